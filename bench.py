@@ -26,19 +26,24 @@ value  : frames decoded by all ranks / max-over-ranks wall time of the K steps.
          36; one workgroup per CU), so the chip holds many batches at once -- the
          default keeps min(K, 20) in flight.  --kernel two_wave is the
          one-workgroup-per-block kernel (lowest latency for a batch alone; best at
-         3 in flight), measured beside it in "two_wave".  The line also reports
-         the same K steps run one batch at a time ("value_one_batch_at_a_time")
-         and the per-launch device times (launch_ms).
+         3 in flight), measured beside it in "two_wave" (--full).  With --full the
+         line also reports the same K steps run one batch at a time
+         ("value_one_batch_at_a_time") and the per-launch device times (launch_ms).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the line of that timed region (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR also writes what the last timed step decoded as DIR/*.npy
+(dump_outputs below).  Everything else is behind --full:
 
 Before the timed region every copy's output is overwritten with 0x7F bytes and its
-block statuses marked unwritten (wvg_batch_poison); right after it every in-flight
-copy -- whose last decode is a timed one -- is downloaded and checked (C2): its int32
-output must equal the generator's PCM bit for bit, every block's status must have
-been stored by a decode, every block's CRC must match (crc_errors == 0), and the
+block statuses marked unwritten (wvg_batch_poison); with --full, right after it every
+in-flight copy -- whose last decode is a timed one -- is downloaded and checked (C2):
+its int32 output must equal the generator's PCM bit for bit, every block's status must
+have been stored by a decode, every block's CRC must match (crc_errors == 0), and the
 blocks handed back by the lane kernel to its fallback (WVG_ST_REDONE) are counted
 ("redo_blocks").
 
-Also printed in the same JSON line:
+Also printed in the same JSON line with --full:
   roofline     : algorithmic bytes per launch (compressed bytes in + int32
                  out) / mean device time per launch measured
                  with hipEvents on the decode stream, vs 8 TB/s HBM peak.
@@ -309,6 +314,45 @@ def verify(batches, pcm) -> dict:
             "pcm_equal": True if pcm is not None else None}
 
 
+DUMP_SAMPLES = 1 << 21  # --dump-outputs: int32 outputs beyond this many are sampled (16 MB as float64)
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(outdir: str, batches) -> None:
+    """--dump-outputs: what a caller of the timed path receives from the last timed step
+    (the batches that step decoded), as float64 .npy files (int32 values are exact in it):
+      samples.npy       the int32 output of the step's batches, one after another; beyond
+                        DUMP_SAMPLES values a fixed sample of it (DUMP_SEED, sorted positions)
+      sample_index.npy  the position of each of those values in the whole output
+      file_results.npy  one row per file: frames, crc_errors, exception, status_or
+                        (wvg_file_result; -1 in every column for a file that did not open)
+    The inputs are the seeded corpora, so equal arguments give equal files from run to run."""
+    os.makedirs(outdir, exist_ok=True)
+    outs = [bb.download() for bb in batches]
+    total = sum(o.size for o in outs)
+    if total > DUMP_SAMPLES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_SAMPLES))
+    else:
+        idx = np.arange(total, dtype=np.int64)
+    samples = np.empty(idx.size, dtype=np.float64)
+    base = 0
+    for o in outs:
+        lo, hi = np.searchsorted(idx, (base, base + o.size))
+        samples[lo:hi] = o[idx[lo:hi] - base]
+        base += o.size
+    rows = []
+    for bb in batches:
+        for i, info in enumerate(bb.infos):
+            if info.open_ok:
+                r = bb.result(i)
+                rows.append((r.frames, r.crc_errors, r.exception, r.status_or))
+            else:
+                rows.append((-1, -1, -1, -1))
+    np.save(os.path.join(outdir, "samples.npy"), samples)
+    np.save(os.path.join(outdir, "sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "file_results.npy"), np.array(rows, dtype=np.float64).reshape(-1, 4))
+
+
 # ---------------------------------------------------------------------------
 # CPU baseline (BASELINE.md:35-38)
 # ---------------------------------------------------------------------------
@@ -497,7 +541,7 @@ def run_rank(args) -> None:
     def step(k):
         for bb in sets[k % copies]:
             bb.decode()
-    extras = not multi and not args.timed_only  # the one-batch legs beside `value`
+    extras = args.full and not multi and not args.timed_only  # the one-batch legs beside `value`
 
     # setup, untimed: one decode of every copy binds its stream to a hardware queue
     # (a copy's first decode also pays one-time costs: the queue's creation, the code
@@ -533,10 +577,14 @@ def run_rank(args) -> None:
         bb.sync()
     t1 = time.perf_counter()
     _barrier(pg)
-    # the timed decodes were real: every copy's output (poisoned before the timed region,
-    # and each copy's last decode is a timed one), CRCs and kernel routing
-    ver = verify(batches, pcm)
-    ver["checked"] = "right after the timed region; outputs poisoned (0x7F) before it"
+    # --full: the timed decodes were real: every copy's output (poisoned before the timed
+    # region, and each copy's last decode is a timed one), CRCs and kernel routing
+    ver = None
+    if args.full:
+        ver = verify(batches, pcm)
+        ver["checked"] = "right after the timed region; outputs poisoned (0x7F) before it"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sets[(args.steps - 1) % copies])
     tsum = tn = 0.0
     for bb in batches:
         ms, n = bb.timed()
@@ -588,11 +636,14 @@ def run_rank(args) -> None:
 
     # PCIe-inclusive rate (host bytes in -> host int32 out, framing included),
     # reported beside `value`, never as it
-    if args.timed_only or multi:  # profiling runs: only the timed region's launches reach the profiler
+    # a plain run ends here, with the line of its timed region; so do profiling runs
+    # (--timed-only: only the timed region's launches reach the profiler) and C5, whose
+    # CPU baseline and end-to-end pass are --full's
+    if not args.full or args.timed_only or multi:
         cpu = None
-        if multi and rank == 0 and not args.no_cpu:
+        if args.full and multi and rank == 0 and not args.no_cpu:
             cpu = cpu_baseline_c5(files, args.cpu_threads)
-        e2e5 = c5_end_to_end(sets, slices) if multi and args.c5_e2e else None
+        e2e5 = c5_end_to_end(sets, slices) if args.full and multi and args.c5_e2e else None
         if rank == 0:
             line = {"metric": METRIC, "value": round(value, 2), "unit": "Msamples/s", "n_gpus": ws,
                     "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -861,6 +912,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the check of their outputs against the generator's PCM, the "
+                         "one-batch and two-wave legs, the PCIe-inclusive requests, the roofline and the CPU baseline "
+                         "(C5: the CPU baseline and the end-to-end pass)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them decoded to DIR/*.npy (dump_outputs)")
     ap.add_argument("--workload", choices=("c2", "c5"), default="c2")
     ap.add_argument("--blocks", type=int, default=1024)
     ap.add_argument("--block-frames", type=int, default=22050)

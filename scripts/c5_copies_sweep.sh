@@ -3,7 +3,7 @@ cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out/c5
 O=gpurun_out/c5/copies.jsonl
 run() {  # $1 = label, rest = bench args
   lab=$1; shift
-  timeout -k 10 300 python bench.py --workload c5 --c5-files 100000 --steps 20 --warmup 2 --no-cpu "$@" > gpurun_out/c5/run.log 2>&1 || { echo "$lab rc=$?"; tail -5 gpurun_out/c5/run.log; exit 1; }
+  timeout -k 10 300 python bench.py --workload c5 --c5-files 100000 --steps 20 --warmup 2 --no-cpu --full "$@" > $(dirname $O)/run.log 2>&1 || { echo "$lab rc=$?"; tail -5 $(dirname $O)/run.log; exit 1; }
   tail -1 gpurun_out/c5/run.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); r={'label':'$lab','ms_per_step':d['ms_per_step'],'value':d['value'],'kernel_ms':d['kernel_ms'],'copies':d['c5_copies'],'slices':d['config']['slices_rank0'],'redo':d['verified']['redo_blocks']}
 print(json.dumps(r)); open('$O','a').write(json.dumps(r)+'\n')"

@@ -26,7 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_share(args, n, r, extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c5", "--c5-files", str(args.files),
-           "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu", "--c5-share", f"{n}:{r}"] + extra
+           "--steps", str(args.steps), "--warmup", str(args.warmup), "--no-cpu", "--full",
+           "--c5-share", f"{n}:{r}"] + extra
     t0 = time.perf_counter()
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
     if p.returncode != 0:

@@ -3,7 +3,7 @@
 # STEPS (in order, the first failing GPU step ends the call):
 #   smoke    __graft_entry__.smoke()
 #   tests    pytest -m gpu (TESTS: files, default tests/; PYTEST_ARGS: extra args, e.g. -k)
-#   bench    bench.py (BENCH_ARGS, default the driver's --steps 20 --warmup 5) -> gpurun_out/g/bench.log
+#   bench    bench.py (BENCH_ARGS, default --steps 20 --warmup 5 --full: the summary reads --full's fields)
 #   ab       for each build in LIBS (paths under wavpackdecoder_amd/): bench.py --no-cpu and
 #            bench_configs.py $CFGS, via WVG_LIB (A/B of experiment builds)
 #   configs  bench_configs.py $CFGS --kernel $KERNEL --inflight $INFLIGHT -> gpurun_out/g/configs.jsonl
@@ -24,13 +24,14 @@ for step in $STEPS; do
     timeout -k 10 1000 python -u -m pytest ${TESTS:-tests/} -m gpu -x -q --timeout 300 --timeout-method thread ${PYTEST_ARGS} > $G/pytest.log 2>&1 || fail tests $? $G/pytest.log
     tail -2 $G/pytest.log ;;
   bench)
-    timeout -k 10 400 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > $G/bench.log 2>&1 || fail bench $? $G/bench.log
+    timeout -k 10 400 python bench.py ${BENCH_ARGS:---steps 20 --warmup 5 --full} > $G/bench.log 2>&1 || fail bench $? $G/bench.log
     tail -1 $G/bench.log | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('bench', d['value'], 'alone', d['launch_ms']['alone'], 'in-flight', d['launch_ms']['in_flight_mean'],
       'one-at-a-time', d.get('value_one_batch_at_a_time'), 'verified', d.get('verified'))" ;;
   ab)
+    AB_ARGS="--full ${AB_ARGS}"  # (the lines below read launch_ms and verified)
     i=0
     for L in ${LIBS:-build/libwvgpu.so}; do
       i=$((i+1))

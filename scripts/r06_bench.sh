@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out/g
 G=gpurun_out/g
 s=$(date +%s)
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $G/bench.log 2>&1 || { tail -20 $G/bench.log; exit 1; }
+timeout -k 10 500 python bench.py --steps 20 --warmup 5 --full > $G/bench.log 2>&1 || { tail -20 $G/bench.log; exit 1; }
 echo "bench wall $(( $(date +%s) - s )) s"
 tail -1 $G/bench.log | python3 -c "
 import json, sys

@@ -29,7 +29,8 @@ def _bench(args):
 
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_c2_weak():
-    d = _bench(["--steps", "4", "--warmup", "1", "--inflight", "4", "--no-cpu", "--timed-only", "--blocks", "256"])
+    d = _bench(["--steps", "4", "--warmup", "1", "--inflight", "4", "--no-cpu", "--timed-only", "--blocks", "256",
+                "--full"])  # (--full: the check of the timed decodes, `verified`)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     v = d["verified"]
     assert v["crc_errors"] == 0 and v["redo_blocks"] == 0 and v["unwritten_blocks"] == 0 and v["pcm_equal"]
@@ -37,6 +38,7 @@ def test_bench_two_ranks_c2_weak():
 
 @pytest.mark.timeout(300)
 def test_bench_two_ranks_c5_strong():
-    d = _bench(["--workload", "c5", "--c5-files", "400", "--steps", "2", "--warmup", "1", "--no-cpu"])
+    d = _bench(["--workload", "c5", "--c5-files", "400", "--steps", "2", "--warmup", "1", "--no-cpu",
+                "--full"])  # (--full: the check of the timed decodes and the end-to-end pass, as before)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
     assert d["config"]["frames_total"] > d["config"]["frames_rank0"] > 0
