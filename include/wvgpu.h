@@ -287,6 +287,48 @@ uint8_t *wvg_batch_host_pcm(wvg_batch *b);
  * batched, overlapped form.) */
 int wvg_batch_download_pcm_async(wvg_batch *b);
 
+/* ---- The stored MD5 sums, verified on the device (beyond the reference, which skips
+ * ID_MD5_CHECKSUM as optional data; `wvunpack -v -m` is the WavPack tool's form).
+ * WavPack stores the MD5 of the source audio bytes -- little-endian at
+ * bytes_per_sample, one-byte PCM unsigned, DSD the raw bytes: WavpackFormatSamples'
+ * forms (WavPackUtils.cs:288-341) -- in a 16-byte sub-block of the last audio block or
+ * of a zero-sample block after it.  wvg_batch_md5 hashes every file's int32 output in
+ * that form, one lane per file (wv_md5.hip), after the whole of the batch's last decode;
+ * it needs neither wvg_batch_format nor a download, returns without waiting
+ * (wvg_batch_sync covers it; the next reset / upload waits for it), and only the
+ * digests (16 bytes a file) come back to the host.  Float files hash their float32 bit
+ * patterns (4 bytes a value) under WVG_OPEN_EXACT_FLOAT.
+ * Known limit: MD5 is a serial chain, so the kernel takes as long as its longest file
+ * at one lane's rate -- measured 57 MB/s of audio bytes per lane, where hashlib does
+ * 1,050 MB/s on one host thread (DESIGN.md §5 "MD5 on the device") -- and pays off for
+ * batches of many files: 4,000 C5 files (255 MB of audio) hash in 5.6 ms.
+ * verdict, from framing facts only: NONE without a stored sum; NOT_COMPARABLE when a sum
+ * is stored but this decode cannot reproduce the source bytes (a hybrid file without its
+ * .wvc, lossy INT32 / float blocks, a float file without WVG_OPEN_EXACT_FLOAT, a file
+ * added with wvg_batch_add_file_at or reduced by OPEN_2CH_MAX); else MATCH / MISMATCH
+ * (a CRC error, a mute or an exception changes the output: MISMATCH).  `computed` is
+ * always filled; `bytes` is the hashed length. */
+#define WVG_MD5_NONE 0
+#define WVG_MD5_MATCH 1
+#define WVG_MD5_MISMATCH 2
+#define WVG_MD5_NOT_COMPARABLE 3
+typedef struct {
+    uint8_t computed[16];
+    uint8_t stored[16];
+    int32_t has_stored;
+    int32_t verdict;
+    int64_t bytes;
+} wvg_file_md5;
+int wvg_batch_md5(wvg_batch *b, void *stream);                     /* after wvg_batch_decode */
+int wvg_batch_file_md5(wvg_batch *b, int file, wvg_file_md5 *out); /* after wvg_batch_sync / wvg_batch_download;
+                                                                      WVG_ERR_ARG: no wvg_batch_md5 since the last
+                                                                      upload; WVG_ERR_OPEN: the file did not open */
+/* host only: the stored sum of a file (the last one; a trailing zero-sample block's
+ * included): 1 found, 0 none, WVG_ERR_OPEN */
+int wvg_probe_file_md5(const uint8_t *file, size_t len, uint8_t stored[16]);
+/* the kernel's MD5 core (wv_md5.h) run on the host over `len` bytes */
+int wvg_md5_bytes(const uint8_t *data, size_t len, uint8_t digest[16]);
+
 /* WvDemo.Main (WvDemo.cs:15-168) for one file of a formatted batch built with
  * chunk_frames 4096: the .wav bytes it writes (stored RIFF header or the
  * synthesized RIFF/fmt/data headers, the PCM, the stored trailer) and its exit

@@ -73,6 +73,9 @@ struct wvenc_params {
     int32_t float_exact;       // float_data: the input ints are float32 bit patterns, split per block into
                                // the integers and a classic wvx stream (float_split); with wvc the wvx
                                // stream goes into the .wvc block
+    int32_t write_md5;         // ID_MD5_CHECKSUM (the caller's digest of the source bytes): 0 none, 1 in the last
+                               // audio block, 2 in a trailing zero-sample metadata block (where WavPack puts it)
+    uint8_t md5[16];
 };
 
 struct wvenc_dsd_params {
@@ -85,6 +88,8 @@ struct wvenc_dsd_params {
     int32_t history_bits;  // mode 1: 0..5
     int32_t rle_tables;    // mode 1: RLE-coded probability tables (else raw 0xFF form)
     int32_t rate_i;        // mode 3
+    int32_t write_md5;     // as wvenc_params
+    uint8_t md5[16];
 };
 }
 
@@ -600,6 +605,21 @@ void write_header(std::vector<uint8_t> &blk, int version, int64_t total, int64_t
     h[29] = (uint8_t)(crc >> 8);
     h[30] = (uint8_t)(crc >> 16);
     h[31] = (uint8_t)(crc >> 24);
+}
+
+// ID_MD5_CHECKSUM (the MD5 of the source audio bytes, handed in by the caller): in
+// the last audio block's metadata, or -- WavPack's own layout -- in a zero-sample
+// block after it, which the reference's walk never reaches (WavPackUtils.cs:277)
+void put_md5(std::vector<uint8_t> &md, const uint8_t *md5) {
+    put_subblock(md, ID_MD5_CHECKSUM, std::vector<uint8_t>(md5, md5 + 16));
+}
+
+void append_md5_block(std::vector<uint8_t> &file, const uint8_t *md5, int version, int64_t total, int64_t block_index,
+                      uint32_t flags, bool total_unknown) {
+    std::vector<uint8_t> blk(32);
+    put_md5(blk, md5);
+    write_header(blk, version, total, block_index, 0, flags, -1, total_unknown);
+    file.insert(file.end(), blk.begin(), blk.end());
 }
 
 std::vector<uint8_t> riff_header(int nch, int bps, int bits, int rate, int64_t frames) {
@@ -1208,6 +1228,7 @@ struct PcmEncoder {
                 put_subblock(md, P.wvx == 2 ? ID_WVX_NEW_BITSTREAM : ID_WVX_BITSTREAM, pl);
             }
             if (bi == nblocks - 1 && P.write_riff) put_subblock(md, ID_RIFF_TRAILER, std::vector<uint8_t>{'t', 'r'});
+            if (bi == nblocks - 1 && P.write_md5 == 1) put_md5(md, P.md5);
 
             int mag = P.mag_override >= 0 ? P.mag_override : count_bits_u32(maxabs);
             if (mag > 31) mag = 31;
@@ -1230,6 +1251,9 @@ struct PcmEncoder {
                              P.block_index_start + f0, (uint32_t)nf, flags, crc_exact, P.total_unknown);
                 wvc_file.insert(wvc_file.end(), cblk.begin(), cblk.end());
             }
+            if (bi == nblocks - 1 && P.write_md5 == 2)
+                append_md5_block(file, P.md5, P.version, P.total_override > 0 ? P.total_override : frames,
+                                 P.block_index_start + f0 + nf, flags, P.total_unknown);
         }
         return file;
     }
@@ -1470,10 +1494,12 @@ std::vector<uint8_t> encode_dsd(const wvenc_dsd_params &P, const uint8_t *x, int
             for (int c = 0; c < wch; c++) crc = add32(crc, add32(shl32(crc, 1), xb[f * P.nch + c]));
         std::vector<uint8_t> md;
         put_subblock(md, ID_DSD_BLOCK, payload);
+        if (bi == nblocks - 1 && P.write_md5 == 1) put_md5(md, P.md5);
         std::vector<uint8_t> blk(32);
         blk.insert(blk.end(), md.begin(), md.end());
         write_header(blk, 0x410, frames, f0, (uint32_t)nf, flags, crc, false);
         file.insert(file.end(), blk.begin(), blk.end());
+        if (bi == nblocks - 1 && P.write_md5 == 2) append_md5_block(file, P.md5, 0x410, frames, f0 + nf, flags, false);
     }
     return file;
 }

@@ -40,13 +40,14 @@ class _Params(ctypes.Structure):
             "int32_zeros", "write_riff", "config_flags", "write_history", "reset_state", "block_index_start",
             "total_unknown", "extras", "mag_override", "int32_sent_bits", "int32_ones", "int32_dups", "wvx",
             "wvx_max_width", "wvx_short")] + [("total_override", ctypes.c_int64), ("sticky_passes", ctypes.c_int32), ("wvc", ctypes.c_int32),
-                                                          ("float_exact", ctypes.c_int32)]
+                                                          ("float_exact", ctypes.c_int32),
+                                                          ("write_md5", ctypes.c_int32), ("md5", ctypes.c_uint8 * 16)]
 
 
 class _DsdParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "nch", "false_stereo", "mode", "block_samples", "rate_multiplier_log2", "sample_rate",
-        "history_bits", "rle_tables", "rate_i")]
+        "history_bits", "rle_tables", "rate_i", "write_md5")] + [("md5", ctypes.c_uint8 * 16)]
 
 
 @dataclass
@@ -89,6 +90,10 @@ class EncParams:
     sticky_passes: bool = False  # blocks after the first continue the decoder's passes (no pass metadata)
     wvc: bool = False            # hybrid: also write the .wvc correction file (encode_pcm_wvc)
     float_exact: bool = False    # float_data: samples are float32 bit patterns (encode_float_exact)
+    # ID_MD5_CHECKSUM: 0 none, 1 in the last audio block, 2 in a trailing zero-sample block;
+    # md5 is the caller's digest (source_md5) -- the encoder never computes one
+    write_md5: int = 0
+    md5: bytes = b""
 
     def to_c(self) -> _Params:
         p = _Params()
@@ -107,7 +112,32 @@ class EncParams:
         for n in ("hybrid", "hybrid_bitrate", "hybrid_balance", "float_data", "write_riff", "write_history",
                   "reset_state", "total_unknown", "sticky_passes", "wvc", "float_exact"):
             setattr(p, n, int(bool(getattr(self, n))))
+        _set_md5(p, self.write_md5, self.md5)
         return p
+
+
+def _set_md5(p, write_md5: int, md5: bytes) -> None:
+    p.write_md5 = int(write_md5)
+    if p.write_md5:
+        if len(md5) != 16:
+            raise ValueError("write_md5 needs the 16-byte digest in md5")
+        p.md5[:] = md5
+
+
+def source_md5(samples: np.ndarray, bytes_per_sample: int, dsd: bool = False) -> bytes:
+    """The digest WavPack stores (ID_MD5_CHECKSUM): hashlib's MD5 of the source audio in
+    its native byte form -- little-endian at bytes_per_sample 1..4, one-byte PCM as
+    unsigned (value + 128), DSD the raw bytes (WavpackFormatSamples' forms,
+    WavPackUtils.cs:288-341).  float32 sources: pass their bit patterns at 4 bytes."""
+    import hashlib
+    if dsd:
+        return hashlib.md5(np.ascontiguousarray(samples, dtype=np.uint8).tobytes()).digest()
+    x = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1)
+    if bytes_per_sample == 1:
+        b = ((x + 128) & 0xFF).astype(np.uint8)
+    else:
+        b = x.astype("<i4").view(np.uint8).reshape(-1, 4)[:, :bytes_per_sample]
+    return hashlib.md5(np.ascontiguousarray(b).tobytes()).digest()
 
 
 def encode_pcm_parallel(samples: np.ndarray, params: EncParams, workers: int | None = None) -> bytes:
@@ -129,7 +159,8 @@ def encode_pcm_parallel(samples: np.ndarray, params: EncParams, workers: int | N
     jobs = []
     for k in range(0, nblocks, per):
         p = dataclasses.replace(params, block_index_start=params.block_index_start + k * B, total_override=frames,
-                                write_riff=params.write_riff and k == 0)
+                                write_riff=params.write_riff and k == 0,
+                                write_md5=params.write_md5 if k + per >= nblocks else 0)
         jobs.append((x[k * B:(k + per) * B], p))
     with ProcessPoolExecutor(max_workers=workers) as ex:
         parts = list(ex.map(_encode_job, jobs))
@@ -230,6 +261,8 @@ class DsdParams:
     history_bits: int = 5
     rle_tables: bool = False
     rate_i: int = 3
+    write_md5: int = 0   # as EncParams
+    md5: bytes = b""
 
     def to_c(self) -> _DsdParams:
         p = _DsdParams()
@@ -237,6 +270,7 @@ class DsdParams:
             setattr(p, n, int(getattr(self, n)))
         p.false_stereo = int(self.false_stereo)
         p.rle_tables = int(self.rle_tables)
+        _set_md5(p, self.write_md5, self.md5)
         return p
 
 

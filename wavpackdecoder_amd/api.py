@@ -336,6 +336,18 @@ class DecodeBatch:
         self._check(self._L.wvg_batch_download_pcm(self._b, out.ctypes.data, out.size))
         return out[:n]
 
+    def md5(self, stream=None):
+        """Hash every file's decoded audio on the device (wvg_batch_md5), after the whole of
+        the last decode; needs neither format() nor a download and returns without
+        waiting -- sync() covers it."""
+        self._check(self._L.wvg_batch_md5(self._b, stream))
+
+    def file_md5(self, i: int) -> _L.WvgFileMd5:
+        """File i's digest, stored sum and verdict (wvg_batch_file_md5; after sync())."""
+        r = _L.WvgFileMd5()
+        self._check(self._L.wvg_batch_file_md5(self._b, int(i), ctypes.byref(r)))
+        return r
+
     def wav(self, i: int):
         """WvDemo.Main for file i (WvDemo.cs:15-168): (exit_code, .wav bytes)."""
         n, rc = ctypes.c_int64(), ctypes.c_int32()
@@ -492,6 +504,39 @@ def wv_demo(data: bytes):
         b.decode()
         b.format(dsd=False)
         return b.wav(idx)
+    finally:
+        b.close()
+
+
+MD5_NONE, MD5_MATCH, MD5_MISMATCH, MD5_NOT_COMPARABLE = (_L.WVG_MD5_NONE, _L.WVG_MD5_MATCH, _L.WVG_MD5_MISMATCH,
+                                                         _L.WVG_MD5_NOT_COMPARABLE)
+
+
+def probe_md5(data: bytes):
+    """The MD5 sum a .wv file stores (ID_MD5_CHECKSUM; host only, wvg_probe_file_md5):
+    16 bytes, None when it stores none; ValueError when the file does not open."""
+    data = bytes(data)
+    out = (ctypes.c_uint8 * 16)()
+    rc = _L.lib().wvg_probe_file_md5(data, len(data), out)
+    if rc < 0:
+        raise ValueError("the file does not open")
+    return bytes(out) if rc == 1 else None
+
+
+def verify_files(files, open_flags: int = 0) -> list:
+    """Decode `files` and check each against its stored MD5 on the device: add, upload,
+    decode, md5 and sync, with no PCM formatted or downloaded (16 bytes a file come
+    back).  Returns one WvgFileMd5 per file (verdict MD5_*), None for a file that did
+    not open."""
+    if not len(files):
+        return []
+    b = DecodeBatch(SAMPLE_BUFFER_SIZE)
+    try:
+        idx = b.add_files(files, open_flags)
+        b.decode()
+        b.md5()
+        b.sync()
+        return [b.file_md5(i) if i >= 0 else None for i in idx]
     finally:
         b.close()
 

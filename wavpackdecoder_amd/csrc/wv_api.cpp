@@ -18,6 +18,7 @@
 #include "wv_desc.h"
 #include "wv_format.h"
 #include "wv_framing.h"
+#include "wv_md5.h"
 
 namespace wvg {
 hipError_t launch_decode(const BlockDesc *descs, const uint32_t *pcm_list, uint32_t n_pcm, const uint32_t *dsd_list,
@@ -32,6 +33,7 @@ hipError_t launch_2wave(int ts, const BlockDesc *descs, const uint32_t *list, ui
                         int32_t *out, uint32_t *status, uint32_t *aux, hipStream_t s, int lane_mode,
                         const uint32_t *lane_list, uint32_t lane_n, uint32_t *lane_dbg);
 hipError_t launch_format(const FormatSeg *segs, uint32_t nseg, const int32_t *in, uint8_t *out, int dsd, hipStream_t s);
+hipError_t launch_md5(const Md5Job *jobs, uint32_t njobs, const int32_t *out, uint8_t *digests, hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
 hipError_t launch_zero_fill(const ZeroSeg *segs, uint32_t nseg, int32_t *out, hipStream_t s);
 hipError_t upload_dsd_ptables();
@@ -243,6 +245,15 @@ struct wvg_batch {
     };
     std::vector<DevRun> dev_runs;
     size_t cap_dfiles = 0, cap_slots = 0, cap_blkf = 0, cap_blkk = 0, cap_ddescs = 0, cap_drecs = 0;
+    // wvg_batch_md5: one job per opened file, ordered by byte length (built and sent once
+    // per upload), the digests at 16 * file index on the device and, copied behind the
+    // kernel, in page-locked host memory
+    Md5Job *d_md5jobs = nullptr;
+    uint8_t *d_md5 = nullptr;
+    size_t cap_md5jobs = 0, cap_md5 = 0;
+    PinnedBuf md5_stage, hmd5;
+    uint32_t md5_njobs = 0;
+    bool md5_jobs_sent = false, md5_issued = false;
 };
 
 static int hip_fail(wvg_ctx *c, hipError_t e, const char *what) {
@@ -400,6 +411,12 @@ static void free_dev(wvg_batch *b) {
     b->cap_tfile = b->cap_rankf = b->cap_cand = b->cap_cnt = 0;
     hipFree(b->d_ddescs);
     hipFree(b->d_drecs);
+    hipFree(b->d_md5jobs);
+    hipFree(b->d_md5);
+    b->d_md5jobs = nullptr;
+    b->d_md5 = nullptr;
+    b->cap_md5jobs = b->cap_md5 = 0;
+    b->md5_jobs_sent = b->md5_issued = false;
     b->d_dfiles = nullptr;
     b->d_slots = nullptr;
     b->d_blkf = b->d_blkk = nullptr;
@@ -624,6 +641,7 @@ int wvg_batch_reset(wvg_batch *b) {
     b->dfiles.clear();
     b->dev_runs.clear();
     b->framed_dev = b->framed_host = 0;
+    b->md5_jobs_sent = b->md5_issued = false;
     return WVG_OK;
 }
 
@@ -1135,6 +1153,7 @@ int wvg_batch_upload(wvg_batch *b) {
     static const bool trace = getenv("WVG_DFRAME_TRACE") && getenv("WVG_DFRAME_TRACE")[0] == '1';
     const double t_up0 = now_ms();
     b->formatted = false;
+    b->md5_jobs_sent = b->md5_issued = false;
     // the blob is followed by 64 B of 0xFF (the reader's past-end fill)
     HIPCHK(c, blob_push(b));  // what the adds have not sent yet
     if (!b->d_blob) HIPCHK(c, ensure(b->d_blob, b->cap_blob, 64));
@@ -1883,6 +1902,112 @@ int wvg_batch_download_pcm_async(wvg_batch *b) {
             HIPCHK(c, hipMemcpyAsync(b->hpcm.data(), b->d_pcm, (size_t)b->pcm_bytes, hipMemcpyDeviceToHost, b->stream));
     }
     HIPCHK(c, hipEventRecord(b->done, b->stream));  // (wvg_batch_sync and the next quiesce wait for it)
+    return WVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The files' MD5 sums on the device (wv_md5.hip) against the stored ID_MD5_CHECKSUM
+// ---------------------------------------------------------------------------
+int wvg_batch_md5(wvg_batch *b, void *stream) {
+    if (!b || !b->uploaded) return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    const size_t nf = b->finfo.size();
+    if (!b->md5_jobs_sent) {
+        // once per upload: a job per opened file, ordered by byte length so that the 64
+        // lanes of a wave run similar trip counts
+        std::vector<Md5Job> jobs;
+        jobs.reserve(nf);
+        for (size_t i = 0; i < nf; i++) {
+            const FileInfo &fi = b->finfo[i];
+            if (!fi.open_ok) continue;
+            Md5Job j;
+            j.in_off = (uint64_t)b->infos[i].out_offset;
+            j.nvals = (uint64_t)(fi.out_frames * fi.out_nch);
+            j.bps = (uint32_t)(fi.md5_bps >= 1 && fi.md5_bps <= 4 ? fi.md5_bps : 2);
+            j.dsd = fi.dsd_multiplier > 0;
+            j.file = (uint32_t)i;
+            j.pad_ = 0;
+            jobs.push_back(j);
+        }
+        std::stable_sort(jobs.begin(), jobs.end(),
+                         [](const Md5Job &x, const Md5Job &y) { return x.nvals * x.bps < y.nvals * y.bps; });
+        // (the buffers below may still be in use by an md5 of the previous upload only
+        // through a caller's stream: the upload's quiesce waited for it)
+        const size_t jb = sizeof(Md5Job) * (jobs.size() ? jobs.size() : 1), db = 16 * (nf ? nf : 1);
+        if (!b->md5_stage.resize(jb) || !b->hmd5.resize(db)) return WVG_ERR_SPACE;
+        HIPCHK(c, ensure(b->d_md5jobs, b->cap_md5jobs, jb));
+        HIPCHK(c, ensure(b->d_md5, b->cap_md5, db));
+        if (!jobs.empty()) memcpy(b->md5_stage.data(), jobs.data(), sizeof(Md5Job) * jobs.size());
+        memset(b->hmd5.data(), 0, db);
+        b->md5_njobs = (uint32_t)jobs.size();
+        // on the batch stream, behind the upload's copies; `up` is recorded again so that
+        // an md5 on a caller's stream waits for the jobs too
+        if (!jobs.empty())
+            HIPCHK(c, hipMemcpyAsync(b->d_md5jobs, b->md5_stage.data(), sizeof(Md5Job) * jobs.size(),
+                                     hipMemcpyHostToDevice, b->stream));
+        HIPCHK(c, hipMemsetAsync(b->d_md5, 0, db, b->stream));
+        HIPCHK(c, hipEventRecord(b->up, b->stream));
+        b->md5_jobs_sent = true;
+    }
+    // after the whole of the last decode: `done` is recorded once every launch group has
+    // joined the decode's stream (as wvg_batch_format orders itself)
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_md5(b->d_md5jobs, b->md5_njobs, b->d_out, b->d_md5, s));
+    if (nf) HIPCHK(c, hipMemcpyAsync(b->hmd5.data(), b->d_md5, 16 * nf, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
+    b->md5_issued = true;
+    return WVG_OK;
+}
+
+int wvg_batch_file_md5(wvg_batch *b, int file, wvg_file_md5 *out) {
+    if (!b || !out || file < 0 || file >= (int)b->finfo.size() || !b->md5_issued) return WVG_ERR_ARG;
+    const FileInfo &fi = b->finfo[(size_t)file];
+    memset(out, 0, sizeof(*out));
+    if (!fi.open_ok) return WVG_ERR_OPEN;
+    memcpy(out->computed, b->hmd5.data() + 16 * (size_t)file, 16);
+    out->bytes = fi.out_frames * fi.out_nch * (int64_t)(fi.md5_bps >= 1 && fi.md5_bps <= 4 ? fi.md5_bps : 2);
+    out->verdict = WVG_MD5_NONE;
+    if (fi.md5_off >= 0) {
+        out->has_stored = 1;
+        memcpy(out->stored, b->blob.data() + (size_t)(fi.blob_base + (uint64_t)fi.md5_off), 16);
+        out->verdict = !fi.md5_comparable ? WVG_MD5_NOT_COMPARABLE
+                       : memcmp(out->computed, out->stored, 16) == 0 ? WVG_MD5_MATCH
+                                                                     : WVG_MD5_MISMATCH;
+    }
+    return WVG_OK;
+}
+
+int wvg_probe_file_md5(const uint8_t *file, size_t len, uint8_t stored[16]) {
+    if ((!file && len) || !stored) return WVG_ERR_ARG;
+    FramingOutput fo;
+    FileInfo fi;
+    frame_file(file, len, 0, 0, 0, 4096, fo, fi);
+    if (!fi.open_ok) return WVG_ERR_OPEN;
+    if (fi.md5_off < 0) return 0;
+    memcpy(stored, file + fi.md5_off, 16);
+    return 1;
+}
+
+int wvg_md5_bytes(const uint8_t *data, size_t len, uint8_t digest[16]) {
+    if ((!data && len) || !digest) return WVG_ERR_ARG;
+    wvmd5::State s;
+    wvmd5::init(s);
+    const size_t whole = len / 64;
+    for (size_t k = 0; k < whole; k++) {
+        const uint8_t *p = data + 64 * k;
+        uint32_t m[16];
+        for (int j = 0; j < 16; j++)
+            m[j] = (uint32_t)p[4 * j] | ((uint32_t)p[4 * j + 1] << 8) | ((uint32_t)p[4 * j + 2] << 16) |
+                   ((uint32_t)p[4 * j + 3] << 24);
+        wvmd5::transform(s, m);
+    }
+    const uint8_t *tail = data + 64 * whole;
+    const uint32_t ntail = (uint32_t)(len - 64 * whole);
+    wvmd5::finish(s, ntail, (uint64_t)len, [&](uint32_t q) -> uint32_t { return q < ntail ? tail[q] : 0u; });
+    wvmd5::digest(s, digest);
     return WVG_OK;
 }
 

@@ -153,6 +153,17 @@ struct FormatSeg {
     uint32_t bps;      // bytes per sample of the file (WavpackGetBytesPerSample)
 };
 
+// One file of a batch for the MD5 kernel (wv_md5.hip): the lane hashes the file's
+// int32 output in its native byte form and stores the digest at digests[16 * file].
+struct Md5Job {
+    uint64_t in_off;  // first int32 of the file in the batch output
+    uint64_t nvals;   // out_frames x out_nch
+    uint32_t bps;     // bytes hashed per value, 1..4 (4 for exact float)
+    uint32_t dsd;     // one-byte values are raw bytes (else value + 128)
+    uint32_t file;    // the file's index (the jobs are ordered by byte length)
+    uint32_t pad_;
+};
+
 // An output range the reference zero-fills itself: a gap between the frames already
 // returned and the next block's first frame (WavPackUtils.cs:227-251).  The framing
 // records it (FramingOutput::zeros) and every decode writes it (wv_zero_fill), so a

@@ -73,6 +73,7 @@ struct DBlock {
     int32_t num_channels; // ID_CHANNEL_INFO's count, -1 none
     int32_t dsd_mult_log2;  // ID_DSD_BLOCK's rate multiplier (log2), -1 none
     int64_t header_off, header_len, trailer_off, trailer_len;  // file-relative, -1 none
+    int64_t md5_off;      // a 16-byte ID_MD5_CHECKSUM's payload, file-relative, -1 none
 };
 
 enum DFrameWhy : uint32_t {
@@ -149,6 +150,7 @@ struct DState {
     bool five;
     int32_t file_format;    // -1: none
     int64_t header_off, header_len, trailer_off, trailer_len;
+    int64_t md5_off;
 };
 
 WVF_HD void dstate_init(DState &s) {
@@ -176,6 +178,7 @@ WVF_HD void dstate_init(DState &s) {
     s.five = false;
     s.file_format = -1;
     s.header_off = s.header_len = s.trailer_off = s.trailer_len = -1;
+    s.md5_off = -1;
 }
 
 // drop pending reads a later read overwrites completely (wv_framing.cpp drop_pending)
@@ -339,6 +342,9 @@ WVF_HD uint32_t dframe_subblocks(const uint8_t *f, uint64_t len, uint64_t hpos, 
             break;
         case ID_ALT_EXTENSION: break;
         case ID_BLOCK_CHECKSUM: s.five = true; break;
+        case ID_MD5_CHECKSUM:  // the stored sum of the source bytes (optional data to the reference)
+            if (byte_length == 16) s.md5_off = (int64_t)doff;
+            break;
         case ID_WVC_BITSTREAM:
         case ID_WVX_BITSTREAM:
         case ID_WVX_NEW_BITSTREAM: return DF_KIND;  // a second stream: the host frames the file
@@ -575,6 +581,7 @@ WVF_HD void dframe_block(const DFile &fi, uint32_t k, const uint8_t *blob, const
     r.num_channels = -1;
     r.dsd_mult_log2 = -1;
     r.header_off = r.header_len = r.trailer_off = r.trailer_len = -1;
+    r.md5_off = -1;
     DHdr h;
     if (!dframe_header(f, fi.len, hpos, h)) {
         r.why = DF_HEADER;
@@ -606,6 +613,7 @@ WVF_HD void dframe_block(const DFile &fi, uint32_t k, const uint8_t *blob, const
     r.header_len = s.header_len;
     r.trailer_off = s.trailer_off;
     r.trailer_len = s.trailer_len;
+    r.md5_off = s.md5_off;
     // snapshot (wv_framing.cpp Framer::snapshot)
     const uint32_t flags = h.flags;
     d.flags = flags;

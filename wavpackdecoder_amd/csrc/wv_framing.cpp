@@ -112,6 +112,7 @@ class Framer {
     int file_format = 0;
     uint32_t dsd_multiplier = 0;
     int64_t header_off = -1, header_len = 0, trailer_off = -1, trailer_len = 0;
+    int64_t md5_off = -1;  // payload of the last 16-byte ID_MD5_CHECKSUM met (beyond the reference, which skips it)
     // config (WavpackConfig.cs)
     int bits_per_sample = 0, bytes_per_sample = 0, num_channels = 0, float_norm_exp_cfg = 0;
     int64_t cfg_flags = 0, sample_rate = 0, channel_mask = 0;
@@ -726,6 +727,9 @@ class Framer {
             if (m.byte_length < 0 || m.byte_length > m.data_len) throw CsException();
             return true;
         case ID_BLOCK_CHECKSUM: five = true; return true;
+        case ID_MD5_CHECKSUM:  // optional data to the reference; the stored sum of the source bytes here
+            if (m.byte_length == 16) md5_off = m.data_file_off;
+            return true;
         default: return (m.id & ID_OPTIONAL_DATA) != 0;
         }
     }
@@ -1118,7 +1122,7 @@ bool dframe_file_info(const DFile &df, const DBlock *r, FileInfo &info) {
     const int32_t mask0 = r[0].info_mask;
     bool lossy = false, five = false;
     int32_t file_format = 0, dsd_log2 = -1;
-    int64_t hoff = -1, hlen = 0, toff = -1, tlen = 0;
+    int64_t hoff = -1, hlen = 0, toff = -1, tlen = 0, md5 = -1;
     for (uint32_t k = 0; k < df.nblocks; k++) {
         const DBlock &b = r[k];
         if (!b.regular || b.info_mask != mask0 || (b.num_channels >= 0 && b.num_channels != df.num_channels))
@@ -1129,6 +1133,7 @@ bool dframe_file_info(const DFile &df, const DBlock *r, FileInfo &info) {
         if (b.dsd_mult_log2 >= 0) dsd_log2 = b.dsd_mult_log2;
         if (b.header_off >= 0) hoff = b.header_off, hlen = b.header_len;
         if (b.trailer_off >= 0) toff = b.trailer_off, tlen = b.trailer_len;
+        if (b.md5_off >= 0) md5 = b.md5_off;
     }
     const uint64_t blob_base = info.blob_base;
     const int64_t first_desc = info.first_desc;
@@ -1159,6 +1164,10 @@ bool dframe_file_info(const DFile &df, const DBlock *r, FileInfo &info) {
     info.header_len = hlen;
     info.trailer_off = toff;
     info.trailer_len = tlen;
+    // (device-framed files have no .wvc / wvx stream and open with flags 0: frame_file's rule)
+    info.md5_off = md5;
+    info.md5_bps = df.bytes_per_sample;
+    info.md5_comparable = !lossy && !df.is_float && !(df.config_flags & CONFIG_HYBRID_FLAG);
     return true;
 }
 
@@ -1192,6 +1201,38 @@ static void chain_blocks(FramingOutput &out, int64_t first, int64_t count) {
         h.chain_len = h.chain_len ? h.chain_len + 1 : 2;
         d.inherit |= INH_MEMBER;
     }
+}
+
+// The blocks after the one the caller's walk stopped at.  WavPack stores the MD5 sum in a
+// zero-sample block after the last audio block; a call stops once sample_index ==
+// total_samples (WavPackUtils.cs:277), and the call after it, which returns no frames,
+// reads that block only as far as unpack_init lets it (a DSD file's rejects the first
+// zero-sample block; an exception ends the walk anywhere).  Headers back to back from
+// `pos` to the file's end, their sub-blocks searched for a 16-byte ID_MD5_CHECKSUM only;
+// no other state is touched.  Returns the last payload's
+// file offset, -1 when there is none; anything that is not a header where one must
+// start, or a sub-block running past its block, ends the walk silently.
+static int64_t md5_tail_walk(const uint8_t *f, int64_t len, int64_t pos) {
+    int64_t found = -1;
+    DHdr h;
+    while (pos >= 0 && pos + 32 <= len && dframe_header(f, (uint64_t)len, (uint64_t)pos, h)) {
+        const int64_t end = pos + 8 + (int64_t)h.ckSize;
+        if (h.ckSize < 24 || end > len) break;
+        for (int64_t p = pos + 32; p + 2 <= end;) {
+            const uint8_t id = f[p];
+            int64_t bl = (int64_t)f[p + 1] << 1, hl = 2;
+            if (id & ID_LARGE) {
+                if (p + 4 > end) break;
+                bl += ((int64_t)f[p + 2] << 9) + ((int64_t)f[p + 3] << 17);
+                hl = 4;
+            }
+            if (p + hl + bl > end) break;
+            if ((id & 0x3f) == ID_MD5_CHECKSUM && bl - ((id & ID_ODD_SIZE) ? 1 : 0) == 16) found = p + hl;
+            p += hl + bl;
+        }
+        pos = end;
+    }
+    return found;
 }
 
 void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
@@ -1411,6 +1452,11 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
     info.num_desc = (int64_t)out.descs.size() - info.first_desc;
     (void)cur;
     chain_blocks(out, info.first_desc, info.num_desc);
+    info.md5_off = F.md5_off;
+    if (!F.wphdr.error) {
+        const int64_t t = md5_tail_walk(file, (int64_t)len, F.wphdr.stream_position + 8 + (int64_t)F.wphdr.ckSize);
+        if (t >= 0) info.md5_off = t;
+    }
     if (out.chain_tables_only && out.tables.size() > tables0) {
         // this file's mode-1 table areas, compacted to the chained blocks' (same layout
         // and 16-B alignment as snapshot's); the others' offsets are never read
@@ -1439,6 +1485,26 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
             d.crc_lossy = 0;
         }
     }
+    // Can this decode reproduce the source bytes the stored MD5 was taken over?  Not
+    // after a seek or a channel reduction, and only when every block decodes exactly:
+    // a hybrid block needs its .wvc stream, a float block the exact-float output (4
+    // bytes a value) with its wvx stream where its flags call for one, an INT32 block
+    // with sent bits its wvx stream.
+    const bool xf = F.exact_float && info.is_float;
+    info.md5_bps = xf ? 4 : info.bytes_per_sample;
+    bool cmp = seek_to < 0 && F.reduced_channels == 0;
+    for (int64_t k = info.first_desc; cmp && k < info.first_desc + info.num_desc; k++) {
+        const BlockDesc &d = out.descs[(size_t)k];
+        if ((d.flags & HYBRID_FLAG) && !d.wvc_len) cmp = false;
+        if (d.flags & FLOAT_DATA) {
+            const uint32_t need = FLOAT_EXCEPTIONS | FLOAT_ZEROS_SENT | FLOAT_SHIFT_SENT | FLOAT_SHIFT_SAME;
+            if (!(d.xfloat & XF_ON) || (!(d.wvx_state & 1) && (d.xfloat & 0xffu & need))) cmp = false;
+        } else if ((d.flags & INT32_DATA) && d.int32_sent_bits != 0 && !(d.wvx_state & 1)) {
+            cmp = false;
+        }
+    }
+    if (info.is_float && !xf) cmp = false;
+    info.md5_comparable = cmp;
 }
 
 }  // namespace wvg

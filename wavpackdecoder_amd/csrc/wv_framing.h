@@ -44,6 +44,12 @@ struct FileInfo {
     int64_t sample_index0 = 0;  // stream.sample_index when the caller's first (non-discard) call starts
     uint64_t blob_base = 0;     // the file's first byte inside the batch blob (header/trailer offsets are file-relative)
     int64_t header_off = -1, header_len = 0, trailer_off = -1, trailer_len = 0;  // RIFF/ALT header+trailer
+    // the stored MD5 of the source audio (ID_MD5_CHECKSUM, 16 bytes; the last one in the
+    // file, a trailing zero-sample block's included): its file offset, -1 none.  It is
+    // comparable when this decode reproduces the source bytes (lossless, whole, all
+    // channels), md5_bps bytes a value.
+    int64_t md5_off = -1;
+    int32_t md5_comparable = 0, md5_bps = 0;
     // blocks of this file inside the batch descriptor array
     int64_t first_desc = 0, num_desc = 0;
 };
