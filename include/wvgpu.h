@@ -138,6 +138,47 @@ int wvg_batch_add_file_at(wvg_batch *b, const uint8_t *file, size_t len, uint32_
  * WVG_ST_UNSUPPORTED.  Parity: round trip to the encoder's float input. */
 #define WVG_OPEN_EXACT_FLOAT 0x40000000u
 
+/* open_flags bit beyond the reference (which refuses a file of more than two channels,
+ * "only two channels supported!", or with OPEN_2CH_MAX decodes its first stream only):
+ * every channel is decoded.  A multichannel WavPack file is a sequence of block groups
+ * INITIAL_BLOCK .. FINAL_BLOCK, one mono or stereo block per stream; with this flag a
+ * file whose ID_CHANNEL_INFO count N is greater than 2 opens with info.num_channels =
+ * info.reduced_channels = N, and its output is info.out_frames frames of N interleaved
+ * int32 at info.out_offset, channels in stream order (stream s at channel offset
+ * sum(widths[:s]), wvg_batch_file_streams).
+ *   Semantics: stream s is framed exactly as the reference frames, under OPEN_2CH_MAX, a
+ * file in which stream s's blocks are the INITIAL_BLOCK ones -- the same call loop at
+ * chunk_frames, seams, gaps, mute, CRC and exception rules, the stream's own width -- so
+ * stream 0 is bit for bit the reference's OPEN_2CH_MAX output.  out_frames is stream
+ * 0's: a stream that delivers fewer frames leaves zeros, one that delivers more is cut.
+ * The layout (streams and widths) is the first group's and must add up to N (else the
+ * file does not open); a later block of another width is WVG_ST_UNSUPPORTED.
+ * wvg_file_result aggregates over all streams' blocks (exception_frame: the smallest),
+ * wvg_batch_file_blocks lists them stream after stream, wvg_batch_md5 hashes the
+ * N-channel output.  WVG_OPEN_EXACT_FLOAT may be combined (it acts per block).
+ *   Cost: every stream decodes into a staging range of its own inside the batch's int32
+ * output, after the file's visible range (16-byte aligned), and one more kernel weaves
+ * them into the N-channel frames at the end of wvg_batch_decode; wvg_batch_out_ints and
+ * a full wvg_batch_download include the staging (about twice the file's output).
+ *   On a file of at most two channels the flag changes nothing.
+ *   Out of scope (WVG_ERR_ARG): together with OPEN_2CH_MAX, wvg_batch_add_file_at (seek)
+ * and wvg_batch_add_file_wvc; wvg_stream_open returns NULL; wvg_batch_add_files_device
+ * takes no flags. */
+#define WVG_OPEN_ALL_CHANNELS 0x20000000u
+/* The stream layout of a file opened with WVG_OPEN_ALL_CHANNELS (host only): widths[s] =
+ * ints a frame of stream s (1 or 2; up to `cap` are written), *channel_mask = its
+ * ID_CHANNEL_INFO mask.  Returns the stream count -- 1 for a file of at most two channels
+ * (its own width, the default mask) -- or WVG_ERR_OPEN when the file does not open. */
+int wvg_probe_file_streams(const uint8_t *file, size_t len, int32_t *widths, int cap, uint32_t *channel_mask);
+/* the same for a file of a batch */
+int wvg_batch_file_streams(const wvg_batch *b, int file, int32_t *widths, int cap, uint32_t *channel_mask);
+/* The interleave kernel's tile code (wv_mc.h) run on the host: `frames` frames of
+ * nstreams streams (widths[s] ints a frame each) woven into out[frames x sum(widths)].
+ * wvg_interleave_tile_frames: the frames of one tile for a channel count (1..255). */
+int wvg_interleave_streams(const int32_t *const *streams, const int32_t *widths, int nstreams, int64_t frames,
+                           int32_t *out);
+int wvg_interleave_tile_frames(int channels);
+
 /* A hybrid .wv file with its .wvc correction file: the hybrid blocks decode
  * EXACTLY (lossless) instead of the reference's lossy output.  Beyond the
  * reference (it opens ID_WVC_BITSTREAM, UnpackUtils.cs:96-106, but never reads
@@ -253,7 +294,8 @@ int wvg_batch_file_blocks(wvg_batch *b, int file, int64_t *end_frame, uint32_t *
  * batch stream).  *ms receives the average per decode. */
 int wvg_batch_time(wvg_batch *b, int iters, float *ms);
 
-/* One-shot convenience: frame + upload + decode + download one file. */
+/* One-shot convenience: frame + upload + decode + download one file (open_flags 0: a file of
+ * more than two channels needs a batch and WVG_OPEN_ALL_CHANNELS). */
 int wvg_decode_file(wvg_ctx *ctx, const uint8_t *file, size_t len, int chunk_frames, int32_t *out, int64_t cap_ints,
                     wvg_file_info *info, wvg_file_result *res);
 

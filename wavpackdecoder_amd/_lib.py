@@ -148,6 +148,10 @@ def lib():
         "wvg_batch_file_md5": (i32, [vp, i32, ctypes.POINTER(WvgFileMd5)]),
         "wvg_probe_file_md5": (i32, [ctypes.c_char_p, ctypes.c_size_t, vp]),
         "wvg_md5_bytes": (i32, [vp, ctypes.c_size_t, vp]),
+        "wvg_probe_file_streams": (i32, [ctypes.c_char_p, ctypes.c_size_t, vp, i32, ctypes.POINTER(ctypes.c_uint32)]),
+        "wvg_batch_file_streams": (i32, [vp, i32, vp, i32, ctypes.POINTER(ctypes.c_uint32)]),
+        "wvg_interleave_streams": (i32, [vp, vp, i32, i64, vp]),
+        "wvg_interleave_tile_frames": (i32, [i32]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -173,6 +177,7 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_probe_file", "wvg_format_samples", "wvg_batch_format", "wvg_batch_pcm_bytes", "wvg_batch_pcm_offset",
             "wvg_batch_device_pcm", "wvg_batch_download_pcm", "wvg_batch_host_pcm", "wvg_batch_download_pcm_async",
             "wvg_batch_wav",
+            "wvg_probe_file_streams", "wvg_batch_file_streams", "wvg_interleave_streams", "wvg_interleave_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of
 # letters and underscores only, so it cannot see a name with a digit in the header and

@@ -53,6 +53,9 @@ OPEN_2CH_MAX = 0x8         # Defines.cs:26
 # beyond the reference: float files decode to float32 bit patterns, exact via the wvx stream
 # (WVG_OPEN_EXACT_FLOAT, include/wvgpu.h)
 OPEN_EXACT_FLOAT = 0x40000000
+# beyond the reference: a file of more than two channels opens and every channel is decoded
+# (WVG_OPEN_ALL_CHANNELS, include/wvgpu.h); not with OPEN_2CH_MAX, start_sample or wvc
+OPEN_ALL_CHANNELS = 0x20000000
 
 
 class WavpackException(RuntimeError):
@@ -302,6 +305,17 @@ class DecodeBatch:
             raise RuntimeError("file blocks unavailable (download first)")
         return ends[:k], st[:k]
 
+    def file_streams(self, i: int):
+        """(widths, channel_mask) of file i (wvg_batch_file_streams): the ints a frame of each
+        stream of a file opened with OPEN_ALL_CHANNELS, in channel order; ([its width],
+        the default mask) for an ordinary file."""
+        w = np.zeros(256, dtype=np.int32)
+        mask = ctypes.c_uint32()
+        n = self._L.wvg_batch_file_streams(self._b, int(i), w.ctypes.data, w.size, ctypes.byref(mask))
+        if n < 0:
+            self._check(n)
+        return w[:n].tolist(), int(mask.value)
+
     def format(self, dsd: bool = False, stream=None):
         """WavpackFormatSamples (WavPackUtils.cs:288-341) over the decoded batch, on the device."""
         self._check(self._L.wvg_batch_format(self._b, int(bool(dsd)), stream))
@@ -521,6 +535,62 @@ def probe_md5(data: bytes):
     if rc < 0:
         raise ValueError("the file does not open")
     return bytes(out) if rc == 1 else None
+
+
+def probe_streams(data: bytes):
+    """(widths, channel_mask) of a file opened with OPEN_ALL_CHANNELS (host only,
+    wvg_probe_file_streams); ValueError when the file does not open."""
+    data = bytes(data)
+    w = np.zeros(256, dtype=np.int32)
+    mask = ctypes.c_uint32()
+    n = _L.lib().wvg_probe_file_streams(data, len(data), w.ctypes.data, w.size, ctypes.byref(mask))
+    if n < 0:
+        raise ValueError("the file does not open")
+    return w[:n].tolist(), int(mask.value)
+
+
+def interleave_tile_frames(channels: int) -> int:
+    """Frames of one tile of the interleave kernel for a channel count (wv_mc.h)."""
+    t = _L.lib().wvg_interleave_tile_frames(int(channels))
+    if t < 0:
+        raise ValueError("channels must be in 1..255")
+    return int(t)
+
+
+def interleave_streams(streams, out: np.ndarray | None = None) -> np.ndarray:
+    """The interleave kernel's tile code run on the host (wvg_interleave_streams): `streams`
+    are int32 arrays of shape (frames, 1 or 2) (or (frames,) for one channel); returns
+    (frames, sum of widths).  out: a flat int32 array to write into (frames x channels)."""
+    arrs = [np.ascontiguousarray(s, dtype=np.int32) for s in streams]
+    arrs = [a.reshape(-1, 1) if a.ndim == 1 else a for a in arrs]
+    frames = arrs[0].shape[0]
+    widths = np.array([a.shape[1] for a in arrs], dtype=np.int32)
+    nch = int(widths.sum())
+    if out is None:
+        out = np.empty(frames * nch, dtype=np.int32)
+    ptrs = (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = _L.lib().wvg_interleave_streams(ctypes.cast(ptrs, ctypes.c_void_p), widths.ctypes.data, len(arrs), frames,
+                                         out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_interleave_streams: {rc}")
+    return out[: frames * nch].reshape(frames, nch)
+
+
+def decode_all_channels(data: bytes, open_flags: int = 0) -> np.ndarray:
+    """Decode one file with every channel (OPEN_ALL_CHANNELS): int32 of shape (frames, N)."""
+    b = DecodeBatch(SAMPLE_BUFFER_SIZE)
+    try:
+        idx = b.add_file(bytes(data), int(open_flags) | OPEN_ALL_CHANNELS)
+        if idx < 0:
+            raise ValueError("the file does not open: " + b.infos[-1].error.decode(errors="replace"))
+        b.decode()
+        out = b.download()
+        b.result(idx)
+        info = b.infos[idx]
+        n = info.out_frames * info.reduced_channels
+        return out[info.out_offset: info.out_offset + n].reshape(-1, info.reduced_channels).copy()
+    finally:
+        b.close()
 
 
 def verify_files(files, open_flags: int = 0) -> list:

@@ -18,6 +18,7 @@
 #include "wv_desc.h"
 #include "wv_format.h"
 #include "wv_framing.h"
+#include "wv_mc.h"
 #include "wv_md5.h"
 
 namespace wvg {
@@ -34,6 +35,8 @@ hipError_t launch_2wave(int ts, const BlockDesc *descs, const uint32_t *list, ui
                         const uint32_t *lane_list, uint32_t lane_n, uint32_t *lane_dbg);
 hipError_t launch_format(const FormatSeg *segs, uint32_t nseg, const int32_t *in, uint8_t *out, int dsd, hipStream_t s);
 hipError_t launch_md5(const Md5Job *jobs, uint32_t njobs, const int32_t *out, uint8_t *digests, hipStream_t s);
+hipError_t launch_mc(const McJob *jobs, uint32_t njobs, const McStreamDev *streams, int32_t *out, int plain,
+                     hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
 hipError_t launch_zero_fill(const ZeroSeg *segs, uint32_t nseg, int32_t *out, hipStream_t s);
 hipError_t upload_dsd_ptables();
@@ -254,6 +257,13 @@ struct wvg_batch {
     PinnedBuf md5_stage, hmd5;
     uint32_t md5_njobs = 0;
     bool md5_jobs_sent = false, md5_issued = false;
+    // the multichannel interleave (wv_mc.h): one job per (file, frame tile) and the files'
+    // stream tables, built and sent once per upload; run at the end of every decode
+    McJob *d_mcjobs = nullptr;
+    McStreamDev *d_mcstreams = nullptr;
+    size_t cap_mcjobs = 0, cap_mcstreams = 0;
+    uint32_t mc_njobs = 0;
+    int mc_plain = 0;  // WVG_MC_PLAIN=1: the strided-store kernel instead of the LDS tile one (A/B)
 };
 
 static int hip_fail(wvg_ctx *c, hipError_t e, const char *what) {
@@ -352,6 +362,8 @@ wvg_batch *wvg_batch_new(wvg_ctx *c, int chunk_frames) {
     }
     const char *fl = getenv("WVG_FORCE_LANE");
     b->force_lane = fl && fl[0] == '1';
+    const char *mp = getenv("WVG_MC_PLAIN");
+    b->mc_plain = mp && mp[0] == '1';
     const char *pp = getenv("WVG_PIPE");
     b->prefer_pipe = pp ? atoi(pp) : 0;
     // the decorr/entropy values of each block are parsed on the device (wv_meta_parse);
@@ -411,6 +423,12 @@ static void free_dev(wvg_batch *b) {
     b->cap_tfile = b->cap_rankf = b->cap_cand = b->cap_cnt = 0;
     hipFree(b->d_ddescs);
     hipFree(b->d_drecs);
+    hipFree(b->d_mcjobs);
+    hipFree(b->d_mcstreams);
+    b->d_mcjobs = nullptr;
+    b->d_mcstreams = nullptr;
+    b->cap_mcjobs = b->cap_mcstreams = 0;
+    b->mc_njobs = 0;
     hipFree(b->d_md5jobs);
     hipFree(b->d_md5);
     b->d_md5jobs = nullptr;
@@ -535,6 +553,7 @@ static void fill_info(const FileInfo &fi, wvg_file_info &wi) {
 
 int wvg_probe_file(const uint8_t *file, size_t len, uint32_t open_flags, int chunk_frames, wvg_file_info *info) {
     if ((!file && len) || !info) return WVG_ERR_ARG;
+    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && (open_flags & wvf::OPEN_2CH_MAX)) return WVG_ERR_ARG;
     FramingOutput fo;
     FileInfo fi;
     frame_file(file, len, 0, 0, open_flags, chunk_frames > 0 ? chunk_frames : 4096, fo, fi);
@@ -602,6 +621,8 @@ static int commit_file(wvg_batch *b, FileInfo &fin, size_t len, wvg_file_info *i
 static int add_file(wvg_batch *b, const uint8_t *file, size_t len, uint32_t open_flags, int64_t seek_to,
                     wvg_file_info *info) {
     if (!b || (!file && len)) return WVG_ERR_ARG;
+    // all channels: neither with the channel reduction nor after a seek
+    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && ((open_flags & wvf::OPEN_2CH_MAX) || seek_to >= 0)) return WVG_ERR_ARG;
     b->uploaded = b->formatted = false;
     size_t base = (b->blob.size() + 15) & ~(size_t)15;
     if (!blob_resize(b, base + len)) {
@@ -721,7 +742,18 @@ static void parallel_copy(uint8_t *blob, const uint8_t *const *files, const size
 // Append one file framed by frame_threaded to the batch at the current output
 // end and commit it (at: its reserved file slot, or -1 for a new one).
 static int merge_framed(wvg_batch *b, FramingOutput &f, FileInfo &fi, size_t len, wvg_file_info *info, int at) {
-    const uint64_t ob = (uint64_t)b->out_ints;
+    uint64_t ob = (uint64_t)b->out_ints;
+    if (!fi.streams.empty()) {
+        // a multichannel file's descriptors and zero fills all lie in its staging ranges, framed
+        // at multiples of 4 ints from base 0: they move to the next multiple of 4 at or after the
+        // file's visible range start (which stays at out_ints), so the ranges stay 16-byte aligned
+        ob = (ob + 3) & ~(uint64_t)3;
+        for (McStream &m : fi.streams) {
+            m.stage_off += (int64_t)ob;
+            m.first_desc += (int64_t)b->fo.descs.size();
+        }
+        fi.mc_end += (int64_t)ob;
+    }
     const uint32_t d0 = (uint32_t)b->fo.descs.size(), i0 = (uint32_t)b->fo.items.size();
     const size_t t0 = (b->fo.tables.size() + 15) & ~(size_t)15;
     for (BlockDesc &d : f.descs) {
@@ -753,6 +785,7 @@ static int merge_framed(wvg_batch *b, FramingOutput &f, FileInfo &fi, size_t len
 int wvg_batch_add_files(wvg_batch *b, int n, const uint8_t *const *files, const size_t *lens, uint32_t open_flags,
                         int threads, wvg_file_info *infos, int32_t *indices) {
     if (!b || n < 0 || (n && (!files || !lens))) return WVG_ERR_ARG;
+    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && (open_flags & wvf::OPEN_2CH_MAX)) return WVG_ERR_ARG;
     b->uploaded = b->formatted = false;
     std::vector<size_t> base((size_t)n);
     size_t end = b->blob.size();
@@ -810,6 +843,7 @@ int wvg_batch_add_files(wvg_batch *b, int n, const uint8_t *const *files, const 
 int wvg_batch_add_file_wvc(wvg_batch *b, const uint8_t *file, size_t len, const uint8_t *wvc, size_t wvc_len,
                            uint32_t open_flags, wvg_file_info *info) {
     if (!b || (!file && len) || (!wvc && wvc_len)) return WVG_ERR_ARG;
+    if (open_flags & wvf::OPEN_ALL_CHANNELS) return WVG_ERR_ARG;  // (no .wvc for multichannel files)
     b->uploaded = b->formatted = false;
     const size_t base = (b->blob.size() + 15) & ~(size_t)15;
     const size_t cbase = (base + len + 15) & ~(size_t)15;
@@ -1173,6 +1207,24 @@ int wvg_batch_upload(wvg_batch *b) {
                   al(sizeof(MetaJob) * b->fo.jobs.size()) + al(b->fo.tables.size()) + al(sizeof(uint32_t) * (nd + 1)) +
                   al(sizeof(uint32_t) * b->pcm_list.size()) + al(sizeof(uint32_t) * b->dsd_list.size()) +
                   al(sizeof(ZeroSeg) * b->fo.zeros.size()) + al(sizeof(FormatSeg) * b->segs.size());
+    // the interleave jobs of the multichannel files and their stream tables
+    std::vector<McJob> mcjobs;
+    std::vector<McStreamDev> mcstreams;
+    for (size_t f = 0; f < b->finfo.size(); f++) {
+        const FileInfo &fi = b->finfo[f];
+        if (!fi.open_ok || fi.streams.empty()) continue;
+        const uint32_t first = (uint32_t)mcstreams.size(), nch = (uint32_t)fi.out_nch;
+        for (const McStream &m : fi.streams)
+            mcstreams.push_back({(uint64_t)m.stage_off, (uint64_t)m.frames, (uint32_t)m.width, (uint32_t)m.ch});
+        const uint64_t tf = mc_tile_frames(nch);
+        for (uint64_t f0 = 0; f0 < (uint64_t)fi.out_frames; f0 += tf) {
+            const uint64_t left = (uint64_t)fi.out_frames - f0;
+            mcjobs.push_back({(uint64_t)b->infos[f].out_offset + f0 * nch, f0, (uint32_t)(left < tf ? left : tf), nch,
+                              first, (uint32_t)fi.streams.size()});
+        }
+    }
+    b->mc_njobs = (uint32_t)mcjobs.size();
+    need += al(sizeof(McJob) * mcjobs.size()) + al(sizeof(McStreamDev) * mcstreams.size());
     build_lane_orders(b);
     for (int t = 0; t < kMaxTermSets; t++)
         need += al(sizeof(uint32_t) * b->ts_list[t].size()) + al(sizeof(uint32_t) * b->ts_lane[t].size());
@@ -1271,6 +1323,12 @@ int wvg_batch_upload(wvg_batch *b) {
         HIPCHK(c, ensure(b->d_ts[t], b->cap_ts[t], sizeof(uint32_t) * (L.size() + LL.size())));
         HIPCHK(c, put(b->d_ts[t], L.data(), sizeof(uint32_t) * L.size()));
         HIPCHK(c, put(b->d_ts[t] + L.size(), LL.data(), sizeof(uint32_t) * LL.size()));
+    }
+    if (b->mc_njobs) {
+        HIPCHK(c, ensure(b->d_mcjobs, b->cap_mcjobs, sizeof(McJob) * mcjobs.size()));
+        HIPCHK(c, ensure(b->d_mcstreams, b->cap_mcstreams, sizeof(McStreamDev) * mcstreams.size()));
+        HIPCHK(c, put(b->d_mcjobs, mcjobs.data(), sizeof(McJob) * mcjobs.size()));
+        HIPCHK(c, put(b->d_mcstreams, mcstreams.data(), sizeof(McStreamDev) * mcstreams.size()));
     }
     // the WavpackFormatSamples segments (wvg_batch_format), so a format issues no copy of its own
     HIPCHK(c, ensure(b->d_segs, b->cap_segs, sizeof(FormatSeg) * (b->segs.empty() ? 1 : b->segs.size())));
@@ -1528,6 +1586,9 @@ int wvg_batch_decode(wvg_batch *b, void *stream) {
         HIPCHK(c, hipStreamWaitEvent(s, b->join[l - 1], 0));
     }
     HIPCHK(c, launch_dsd_fill(b->d_descs, b->d_dsd, (uint32_t)b->dsd_list.size(), b->d_status, b->d_mute, b->d_out, s));
+    // multichannel files: every launch group has joined `s`, the streams' staging ranges are
+    // final -- weave them into the visible ranges before `done`
+    if (b->mc_njobs) HIPCHK(c, launch_mc(b->d_mcjobs, b->mc_njobs, b->d_mcstreams, b->d_out, b->mc_plain, s));
     if (b->timing) HIPCHK(c, hipEventRecord(b->tev.back(), s));
     HIPCHK(c, hipEventRecord(b->done, s));
     b->downloaded = false;
@@ -1683,15 +1744,43 @@ static int64_t first_exception_block(const wvg_batch *b, const FileInfo &fi) {
 
 // frames the file's calls return before the call that throws: the call holding the
 // device-reported frame of the first block that raised (-1: no device exception)
-static int64_t exception_call_frame(const wvg_batch *b, const FileInfo &fi, const wvg_file_info &wi) {
-    const int64_t kx = first_exception_block(b, fi);
-    if (kx < 0) return -1;
-    const int nch = wi.reduced_channels ? wi.reduced_channels : 1;
+// the first output frame of block k of a file: its out_off against the file's output, or,
+// in a multichannel file, against its stream's staging range (nch: ints a frame there)
+static int64_t block_start_frame(const wvg_batch *b, const FileInfo &fi, const wvg_file_info &wi, int64_t k, int &nch) {
+    const BlockDesc &d = b->fo.descs[(size_t)k];
+    for (const McStream &m : fi.streams)
+        if (k >= m.first_desc && k < m.first_desc + m.num_desc) {
+            nch = m.width;
+            return ((int64_t)d.out_off - m.stage_off) / nch;
+        }
+    nch = wi.reduced_channels ? wi.reduced_channels : 1;
+    return ((int64_t)d.out_off - wi.out_offset) / nch;
+}
+
+static int64_t exception_call_frame_of(const wvg_batch *b, const FileInfo &fi, const wvg_file_info &wi, int64_t kx) {
+    int nch = 1;
     const BlockDesc &d = b->fo.descs[(size_t)kx];
-    const int64_t start = ((int64_t)d.out_off - wi.out_offset) / nch;  // block's first output frame
+    const int64_t start = block_start_frame(b, fi, wi, kx, nch);
     const int64_t t = b->h_aux[(size_t)kx];
     if (t < (int64_t)d.first_chunk) return start - (int64_t)d.first_bsp / nch;
     return start + d.first_chunk + (t - d.first_chunk) / d.chunk * d.chunk;
+}
+
+static int64_t exception_call_frame(const wvg_batch *b, const FileInfo &fi, const wvg_file_info &wi) {
+    if (fi.streams.empty()) {
+        const int64_t kx = first_exception_block(b, fi);
+        return kx < 0 ? -1 : exception_call_frame_of(b, fi, wi, kx);
+    }
+    // a multichannel file: the smallest such frame over its streams' first raising blocks
+    int64_t best = -1;
+    for (const McStream &m : fi.streams)
+        for (int64_t k = m.first_desc; k < m.first_desc + m.num_desc; k++)
+            if (b->h_status[(size_t)k] & ST_EXCEPTION) {
+                const int64_t f = exception_call_frame_of(b, fi, wi, k);
+                if (best < 0 || f < best) best = f;
+                break;
+            }
+    return best;
 }
 
 // the status word a block contributes to the file result
@@ -1722,7 +1811,7 @@ int wvg_batch_file_result(wvg_batch *b, int file, wvg_file_result *res) {
         if (st & ST_CRC_ERROR) res->crc_errors++;
         if (st & ST_EXCEPTION) {
             res->exception = 1;
-            break;
+            if (fi.streams.empty()) break;  // (a multichannel file's other streams go on)
         }
     }
     if (res->exception) {
@@ -1742,11 +1831,11 @@ int wvg_batch_file_blocks(wvg_batch *b, int file, int64_t *end_frame, uint32_t *
     const FileInfo &fi = b->finfo[(size_t)file];
     const wvg_file_info &wi = b->infos[(size_t)file];
     if (cap < fi.num_desc) return WVG_ERR_SPACE;
-    const int nch = wi.reduced_channels ? wi.reduced_channels : 1;
     for (int64_t k = 0; k < fi.num_desc; k++) {
         const BlockDesc &d = b->fo.descs[(size_t)(fi.first_desc + k)];
         // out_off is the block's first output frame (a seek's dropped frames lie before the file's output)
-        const int64_t start = ((int64_t)d.out_off - wi.out_offset) / nch;
+        int nch = 1;
+        const int64_t start = block_start_frame(b, fi, wi, fi.first_desc + k, nch);
         if (end_frame) end_frame[k] = start + (int64_t)d.nframes;
         if (status) status[k] = block_verdict(b, fi.first_desc + k);
     }
@@ -1991,6 +2080,75 @@ int wvg_probe_file_md5(const uint8_t *file, size_t len, uint8_t stored[16]) {
     return 1;
 }
 
+// ---- multichannel files (WVG_OPEN_ALL_CHANNELS) ----
+static int put_streams(const std::vector<int32_t> &w, uint32_t mask, int32_t *widths, int cap, uint32_t *channel_mask) {
+    if (widths)
+        for (int i = 0; i < (int)w.size() && i < cap; i++) widths[i] = w[(size_t)i];
+    if (channel_mask) *channel_mask = mask;
+    return (int)w.size();
+}
+
+int wvg_probe_file_streams(const uint8_t *file, size_t len, int32_t *widths, int cap, uint32_t *channel_mask) {
+    if ((!file && len) || cap < 0 || (cap && !widths)) return WVG_ERR_ARG;
+    FramingOutput fo;
+    FileInfo fi;
+    frame_file(file, len, 0, 0, wvf::OPEN_ALL_CHANNELS, 4096, fo, fi);
+    if (!fi.open_ok) return WVG_ERR_OPEN;
+    std::vector<int32_t> w;
+    for (const McStream &m : fi.streams) w.push_back(m.width);
+    uint32_t mask = fi.channel_mask;
+    if (w.empty()) {  // an ordinary file: one stream of its own width, the default mask (WavPackUtils.cs:102-106)
+        w.push_back(fi.out_nch);
+        mask = 0x5u - (uint32_t)(fi.out_nch == 1 ? 1 : 2);
+    }
+    return put_streams(w, mask, widths, cap, channel_mask);
+}
+
+int wvg_batch_file_streams(const wvg_batch *b, int file, int32_t *widths, int cap, uint32_t *channel_mask) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || cap < 0 || (cap && !widths)) return WVG_ERR_ARG;
+    const FileInfo &fi = b->finfo[(size_t)file];
+    if (!fi.open_ok) return WVG_ERR_OPEN;
+    std::vector<int32_t> w;
+    for (const McStream &m : fi.streams) w.push_back(m.width);
+    uint32_t mask = fi.channel_mask;
+    if (w.empty()) {
+        w.push_back(fi.out_nch);
+        mask = 0x5u - (uint32_t)(fi.out_nch == 1 ? 1 : 2);
+    }
+    return put_streams(w, mask, widths, cap, channel_mask);
+}
+
+int wvg_interleave_tile_frames(int channels) {
+    if (channels < 1 || channels > (int)kMcMaxChannels) return WVG_ERR_ARG;
+    return (int)mc_tile_frames((uint32_t)channels);
+}
+
+int wvg_interleave_streams(const int32_t *const *streams, const int32_t *widths, int nstreams, int64_t frames,
+                           int32_t *out) {
+    if (nstreams < 1 || !streams || !widths || frames < 0 || (frames && !out)) return WVG_ERR_ARG;
+    std::vector<McStreamDev> st((size_t)nstreams);
+    uint32_t nch = 0;
+    for (int s = 0; s < nstreams; s++) {
+        if ((widths[s] != 1 && widths[s] != 2) || (frames && !streams[s])) return WVG_ERR_ARG;
+        st[(size_t)s] = {0, (uint64_t)frames, (uint32_t)widths[s], nch};
+        nch += (uint32_t)widths[s];
+        if (nch > kMcMaxChannels) return WVG_ERR_ARG;
+    }
+    // the kernel's tile code (wv_mc.h), the workgroup's threads as a loop
+    std::vector<int32_t> tile(kMcTileInts + 4);
+    int32_t *t = tile.data();
+    while ((uintptr_t)t & 15u) t++;
+    const uint64_t tf = mc_tile_frames(nch);
+    for (uint64_t f0 = 0; f0 < (uint64_t)frames; f0 += tf) {
+        const uint64_t left = (uint64_t)frames - f0;
+        const McJob j = {f0 * nch, f0, (uint32_t)(left < tf ? left : tf), nch, 0, (uint32_t)nstreams};
+        for (int s = 0; s < nstreams; s++)
+            for (uint32_t tid = 0; tid < kMcThreads; tid++) mc_gather(j, st[(size_t)s], streams[s], t, tid, kMcThreads);
+        for (uint32_t tid = 0; tid < kMcThreads; tid++) mc_store(j, t, out + j.out_off, tid, kMcThreads);
+    }
+    return WVG_OK;
+}
+
 int wvg_md5_bytes(const uint8_t *data, size_t len, uint8_t digest[16]) {
     if ((!data && len) || !digest) return WVG_ERR_ARG;
     wvmd5::State s;
@@ -2213,6 +2371,14 @@ static void stream_count_blocks(wvg_stream *s) {
 wvg_stream *wvg_stream_open(wvg_ctx *ctx, const uint8_t *file, size_t len, uint32_t open_flags, int64_t window_frames,
                             wvg_file_info *info) {
     if (!ctx || (!file && len)) return nullptr;
+    if (open_flags & wvf::OPEN_ALL_CHANNELS) {
+        ctx->err = "wvg_stream_open: WVG_OPEN_ALL_CHANNELS is not supported by the stream API";
+        if (info) {
+            memset(info, 0, sizeof(*info));
+            strncpy(info->error, "all channels: not supported by the stream API", sizeof(info->error) - 1);
+        }
+        return nullptr;
+    }
     if (hipSetDevice(ctx->device) != hipSuccess) return nullptr;
     wvg_stream *s = new wvg_stream();
     s->ctx = ctx;

@@ -143,6 +143,11 @@ class Framer {
     int64_t wvc_len = 0, wvc_pos = 0;
     uint64_t wvc_base = 0;
     bool exact_float = false;  // OPEN_EXACT_FLOAT (beyond the reference)
+    // OPEN_ALL_CHANNELS (beyond the reference): the stream selector.  sel >= 0: only the
+    // blocks at position `sel` of their group (INITIAL_BLOCK .. FINAL_BLOCK) are presented,
+    // with INITIAL_BLOCK set in the header copy; the others are stepped over by ckSize
+    int sel = -1;
+    int64_t grp_pos = 1 << 30;  // the last header's position in its group (none seen yet)
 
     Framer() {
         memset(read_buffer, 0, sizeof(read_buffer));
@@ -168,6 +173,18 @@ class Framer {
             bleft = 32;
             if (b[0] == 'w' && b[1] == 'v' && b[2] == 'p' && b[3] == 'k' && (b[4] & 1) == 0 && b[6] < 16 &&
                 b[7] == 0 && b[9] == 4 && b[8] >= (MIN_STREAM_VERS & 0xff) && b[8] <= (MAX_STREAM_VERS & 0xff)) {
+                if (sel >= 0) {
+                    const uint32_t fl = (uint32_t)b[24] | ((uint32_t)b[25] << 8) | ((uint32_t)b[26] << 16) | ((uint32_t)b[27] << 24);
+                    grp_pos = (fl & INITIAL_BLOCK) ? 0 : grp_pos + 1;
+                    if (grp_pos != sel) {  // another stream's block: on to the next header
+                        const int64_t ck = (int64_t)((uint32_t)b[4] | ((uint32_t)b[5] << 8) | ((uint32_t)b[6] << 16));
+                        const int64_t next = in.pos - 32 + 8 + ck;
+                        in.pos = next < in.pos ? in.pos : (next > in.len ? in.len : next);
+                        bleft = 0;
+                        continue;
+                    }
+                    b[25] |= (uint8_t)(INITIAL_BLOCK >> 8);
+                }
                 wphdr.ckSize = (uint32_t)b[4] | ((uint32_t)b[5] << 8) | ((uint32_t)b[6] << 16) | ((uint32_t)b[7] << 24);
                 wphdr.version = (int16_t)((b[9] << 8) | b[8]);
                 wphdr.total_samples = (int64_t)(((uint64_t)b[11] << 32) | ((uint64_t)b[15] << 24) |
@@ -1105,8 +1122,62 @@ void apply_meta_jobs(FramingOutput &out, const uint8_t *blob) {
         for (uint32_t k = 0; k < j.count; k++) meta_apply(out.descs[j.desc], out.items[j.first + k], blob);
 }
 
+bool probe_streams(const uint8_t *file, size_t len, std::vector<int32_t> &widths, int &num_channels,
+                   uint32_t &channel_mask) {
+    widths.clear();
+    num_channels = 0;
+    channel_mask = 0;
+    std::unique_ptr<Framer> FP(new Framer());
+    Framer &F = *FP;
+    F.in.d = file;
+    F.in.len = (int64_t)len;
+    // the first audio block, found as read_next_header finds it (junk before it is skipped);
+    // zero-sample blocks before it are stepped over
+    for (;;) {
+        F.read_next_header();
+        if (F.wphdr.error) return false;
+        if (F.wphdr.block_samples != 0) break;
+        const int64_t next = F.wphdr.stream_position + 8 + (int64_t)F.wphdr.ckSize;
+        if (next > F.in.pos) F.in.pos = next;
+    }
+    if (!(F.wphdr.flags & INITIAL_BLOCK)) return false;
+    int64_t pos = F.wphdr.stream_position;
+    DHdr h;
+    for (bool first = true;; first = false) {
+        if (!dframe_header(file, (uint64_t)len, (uint64_t)pos, h)) break;
+        if (!first && (h.flags & INITIAL_BLOCK)) break;  // (a group without FINAL_BLOCK ends at the next one)
+        const int64_t end = pos + 8 + (int64_t)h.ckSize;
+        if (h.ckSize < 24 || end > (int64_t)len) break;
+        const bool pcm = !(h.flags & DSD_FLAG);
+        widths.push_back(((h.flags & MONO_FLAG) && !(pcm && (h.flags & FALSE_STEREO))) ? 1 : 2);
+        if (first) {
+            for (int64_t p = pos + 32; p + 2 <= end;) {
+                const uint8_t id = file[p];
+                int64_t bl = (int64_t)file[p + 1] << 1, hl = 2;
+                if (id & ID_LARGE) {
+                    if (p + 4 > end) break;
+                    bl += ((int64_t)file[p + 2] << 9) + ((int64_t)file[p + 3] << 17);
+                    hl = 4;
+                }
+                if (p + hl + bl > end) break;
+                const int64_t real = bl - ((id & ID_ODD_SIZE) ? 1 : 0);
+                if ((id & 0x3f) == ID_CHANNEL_INFO && real >= 1 && real <= 5) {
+                    num_channels = file[p + hl];
+                    channel_mask = 0;
+                    for (int64_t k = 1; k < real; k++) channel_mask |= (uint32_t)file[p + hl + k] << (8 * (k - 1));
+                }
+                p += hl + bl;
+            }
+        }
+        if ((h.flags & FINAL_BLOCK) || widths.size() >= 256) break;
+        pos = end;
+    }
+    return !widths.empty();
+}
+
 int64_t file_out_extent(const FramingOutput &out, const FileInfo &info, uint64_t out_base_ints) {
     int64_t extent = info.out_frames * info.out_nch;
+    if (!info.streams.empty() && info.mc_end - (int64_t)out_base_ints > extent) extent = info.mc_end - (int64_t)out_base_ints;
     for (int64_t k = info.first_desc; k < info.first_desc + info.num_desc; k++) {
         const BlockDesc &d = out.descs[(size_t)k];
         const int64_t e = (int64_t)(d.out_off - out_base_ints) + (int64_t)d.nframes * (int64_t)d.out_nch;
@@ -1235,11 +1306,16 @@ static int64_t md5_tail_walk(const uint8_t *f, int64_t len, int64_t pos) {
     return found;
 }
 
-void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
-                int chunk, FramingOutput &out, FileInfo &info, int64_t seek_to, const uint8_t *wvc, size_t wvc_len,
-                uint64_t wvc_base) {
+// One walk of the caller's loop over a file.  sel < 0: the file as the reference opens
+// it.  sel >= 0 (OPEN_ALL_CHANNELS): stream `sel` of a multichannel file, `width` ints a
+// frame -- the reference's OPEN_2CH_MAX walk of a file in which that stream's blocks are
+// the INITIAL_BLOCK ones.
+static void frame_one(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
+                      int chunk, FramingOutput &out, FileInfo &info, int64_t seek_to, const uint8_t *wvc,
+                      size_t wvc_len, uint64_t wvc_base, int sel, int width) {
     std::unique_ptr<Framer> FP(new Framer());
     Framer &F = *FP;
+    F.sel = sel;
     F.defer = out.defer_values;
     F.wvc = wvc;
     F.wvc_len = wvc ? (int64_t)wvc_len : 0;
@@ -1262,6 +1338,7 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
         info.exception = 1;
         return;
     }
+    if (sel >= 0) F.reduced_channels = width;  // (whatever FINAL_BLOCK says: the stream's own width)
     info.open_ok = 1;
     info.num_channels = F.num_channels;
     info.reduced_channels = F.reduced_channels;
@@ -1378,7 +1455,8 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
                         d.pre_chunk = (uint32_t)dchunk;
                         d.out_off = out_base_ints + (uint64_t)(out_frames * nch) - (uint64_t)(rem * nch);
                     }
-                    if (!pcm_blk && (bch != nch || dsd_wch != nch)) {
+                    // (a stream's block that departs from the layout of the file's first group is not decoded)
+                    if ((!pcm_blk && (bch != nch || dsd_wch != nch)) || (sel >= 0 && bch != nch)) {
                         d.kind = KIND_SKIP;
                         d.fstatus |= ST_UNSUPPORTED;
                         d.inherit = d.inherit_passes = 0;
@@ -1410,6 +1488,7 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
                 // cannot see the device's mute state and flags the throw.)
                 const int wch = pcm_blk ? bch : dsd_wch;  // ints a frame the unmuted call writes
                 const bool overrun =
+                    sel >= 0 && bch != nch ? false :
                     (wch == 2 && nch == 1 && buf_idx + 2 * n > buf_len) ||
                     (!pcm_blk && F.dsd.mode == 0 && (hh.flags & FALSE_STEREO) && buf_idx + 3 * n > buf_len);
                 cur->nframes += (uint32_t)n;
@@ -1492,7 +1571,7 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
     // with sent bits its wvx stream.
     const bool xf = F.exact_float && info.is_float;
     info.md5_bps = xf ? 4 : info.bytes_per_sample;
-    bool cmp = seek_to < 0 && F.reduced_channels == 0;
+    bool cmp = seek_to < 0 && (F.reduced_channels == 0 || sel >= 0);
     for (int64_t k = info.first_desc; cmp && k < info.first_desc + info.num_desc; k++) {
         const BlockDesc &d = out.descs[(size_t)k];
         if ((d.flags & HYBRID_FLAG) && !d.wvc_len) cmp = false;
@@ -1505,6 +1584,102 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
     }
     if (info.is_float && !xf) cmp = false;
     info.md5_comparable = cmp;
+}
+
+// OPEN_ALL_CHANNELS on a file of more than two channels: one walk per stream, all into
+// `out`; every stream's descriptors and zero fills are then moved to its staging range
+// after the visible range (out_frames x num_channels ints at out_base_ints).
+static void frame_streams(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints,
+                          uint32_t open_flags, int chunk, FramingOutput &out, FileInfo &info,
+                          const std::vector<int32_t> &widths, int nch, uint32_t mask) {
+    const size_t d0 = out.descs.size(), z0 = out.zeros.size(), t0 = out.tables.size(), i0 = out.items.size(),
+                 j0 = out.jobs.size();
+    const int ns = (int)widths.size();
+    std::vector<FileInfo> si((size_t)ns);
+    std::vector<size_t> zfirst((size_t)ns + 1);
+    for (int s = 0; s < ns; s++) {
+        zfirst[(size_t)s] = out.zeros.size();
+        frame_one(file, len, blob_base, 0, open_flags | OPEN_2CH_MAX, chunk, out, si[(size_t)s], -1, nullptr, 0, 0, s,
+                  widths[(size_t)s]);
+        if (!si[(size_t)s].open_ok) {  // the file does not open: nothing of it stays
+            out.descs.resize(d0);
+            out.zeros.resize(z0);
+            out.tables.resize(t0);
+            out.items.resize(i0);
+            out.jobs.resize(j0);
+            FileInfo f = si[(size_t)s];
+            info = FileInfo();
+            info.error = f.error;
+            info.exception = f.exception;
+            info.first_desc = (int64_t)d0;
+            info.blob_base = blob_base;
+            return;
+        }
+    }
+    zfirst[(size_t)ns] = out.zeros.size();
+    info = si[0];
+    info.num_channels = nch;
+    info.reduced_channels = nch;
+    info.out_nch = nch;
+    info.channel_mask = mask;
+    info.first_desc = (int64_t)d0;
+    info.num_desc = (int64_t)out.descs.size() - (int64_t)d0;
+    // staging: 16-byte aligned ranges after the visible one, each as long as its stream's
+    // descriptors write (a stream that raised the C# exception mid-call keeps that call's)
+    auto al4 = [](int64_t x) { return (x + 3) & ~(int64_t)3; };
+    int64_t cur = al4((int64_t)out_base_ints + info.out_frames * nch);
+    int ch = 0;
+    bool cmp = true;
+    for (int s = 0; s < ns; s++) {
+        const FileInfo &f = si[(size_t)s];
+        McStream m;
+        m.width = widths[(size_t)s];
+        m.ch = ch;
+        ch += m.width;
+        m.stage_off = cur;
+        m.frames = f.out_frames < info.out_frames ? f.out_frames : info.out_frames;
+        m.first_desc = f.first_desc;
+        m.num_desc = f.num_desc;
+        const int64_t extent = file_out_extent(out, f, 0);
+        for (int64_t k = f.first_desc; k < f.first_desc + f.num_desc; k++) out.descs[(size_t)k].out_off += (uint64_t)cur;
+        for (size_t z = zfirst[(size_t)s]; z < zfirst[(size_t)s + 1]; z++) out.zeros[z].off += (uint64_t)cur;
+        cur = al4(cur + extent);
+        info.streams.push_back(m);
+        info.exception |= f.exception;
+        info.nondet |= f.nondet;
+        info.lossy_blocks |= f.lossy_blocks;
+        if (f.md5_off > info.md5_off) info.md5_off = f.md5_off;  // the last one in the file
+        cmp = cmp && f.md5_comparable;
+    }
+    info.mc_end = cur;
+    info.md5_comparable = cmp;
+}
+
+void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
+                int chunk, FramingOutput &out, FileInfo &info, int64_t seek_to, const uint8_t *wvc, size_t wvc_len,
+                uint64_t wvc_base) {
+    const uint32_t flags = open_flags & ~OPEN_ALL_CHANNELS;
+    if (open_flags & OPEN_ALL_CHANNELS) {
+        std::vector<int32_t> widths;
+        int nch = 0;
+        uint32_t mask = 0;
+        // (a file of at most two channels, or one whose first group tells nothing, takes the ordinary walk)
+        if (probe_streams(file, len, widths, nch, mask) && nch > 2) {
+            int sum = 0;
+            for (int32_t w : widths) sum += w;
+            info = FileInfo();
+            info.first_desc = (int64_t)out.descs.size();
+            info.blob_base = blob_base;
+            if (sum != nch)
+                info.error = "channel count does not match the streams of the first block group!";
+            else if (seek_to >= 0 || wvc || (open_flags & OPEN_2CH_MAX))
+                info.error = "all channels: no seek, correction file or channel reduction!";
+            else
+                frame_streams(file, len, blob_base, out_base_ints, flags, chunk, out, info, widths, nch, mask);
+            return;
+        }
+    }
+    frame_one(file, len, blob_base, out_base_ints, flags, chunk, out, info, seek_to, wvc, wvc_len, wvc_base, -1, 0);
 }
 
 }  // namespace wvg

@@ -21,6 +21,17 @@
 
 namespace wvg {
 
+// One stream of a file opened with OPEN_ALL_CHANNELS (a file of more than two channels
+// is a sequence of block groups INITIAL_BLOCK .. FINAL_BLOCK, one mono or stereo block
+// per stream): its blocks decode into a staging range of their own.
+struct McStream {
+    int32_t width = 0;      // ints a frame (1 or 2)
+    int32_t ch = 0;         // its first channel in the file's frames (sum of the widths before it)
+    int64_t stage_off = 0;  // its staging range inside the batch output (ints, a multiple of 4)
+    int64_t frames = 0;     // frames it delivers, cut to the file's out_frames
+    int64_t first_desc = 0, num_desc = 0;
+};
+
 struct FileInfo {
     // WavpackOpenFileInput outcome (WavPackUtils.cs:36-120)
     int32_t open_ok = 0;
@@ -52,6 +63,12 @@ struct FileInfo {
     int32_t md5_comparable = 0, md5_bps = 0;
     // blocks of this file inside the batch descriptor array
     int64_t first_desc = 0, num_desc = 0;
+    // OPEN_ALL_CHANNELS on a file of more than two channels: its streams (empty otherwise;
+    // the descriptors are the streams' one after another), the ID_CHANNEL_INFO mask and
+    // the end of the staging ranges (an int index of the batch output)
+    std::vector<McStream> streams;
+    uint32_t channel_mask = 0;
+    int64_t mc_end = 0;
 };
 
 // DSD fast/high tables live in a side area (bytes) appended per block.
@@ -81,16 +98,29 @@ void apply_meta_jobs(FramingOutput &out, const uint8_t *blob);
 // appended to `out` with out_off relative to `out_base_ints`.
 // seek_to >= 0: the caller calls SetSample(seek_to) (WavPackUtils.cs:509-594)
 // right after opening, and its calls return the frames from there on.
+// open_flags & OPEN_ALL_CHANNELS on a file of more than two channels: every stream is
+// walked on its own (the reference's OPEN_2CH_MAX walk of a file in which that stream's
+// blocks are the INITIAL_BLOCK ones, out_nch = the stream's width) into a staging range
+// after the file's visible range of out_frames x num_channels ints; info.streams
+// describes them (no seek, no .wvc: the file then does not open).
 // wvc (optional): the file's .wvc correction file, whose bytes start at blob
 // offset wvc_base; hybrid blocks then decode exactly (beyond the reference).
 void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
                 int chunk, FramingOutput &out, FileInfo &info, int64_t seek_to = -1, const uint8_t *wvc = nullptr,
                 size_t wvc_len = 0, uint64_t wvc_base = 0);
 
+// The stream layout of a file's first block group: each stream's width (ints a frame, as
+// the framing counts them: PCM FALSE_STEREO is 2), the ID_CHANNEL_INFO count and mask of
+// its first block (0 channels: none stored).  False when no audio block is found or the
+// group does not start with INITIAL_BLOCK.
+bool probe_streams(const uint8_t *file, size_t len, std::vector<int32_t> &widths, int &num_channels,
+                   uint32_t &channel_mask);
+
 // Output ints a batch reserves for a framed file: its reported values
 // (out_frames x out_nch) or more when a descriptor writes past them -- a file
 // that raised the C# exception mid-call keeps the descriptor of that call,
-// whose writes must not reach the next file's range.
+// whose writes must not reach the next file's range.  A multichannel file's
+// extent covers its visible range and its streams' staging.
 int64_t file_out_extent(const FramingOutput &out, const FileInfo &info, uint64_t out_base_ints);
 
 // FileInfo of a file framed on the device (wv_dframe.h) from its walk and its
