@@ -915,10 +915,16 @@ __device__ __forceinline__ LW lword_fast(LState &s, const uint8_t *ring, uint32_
 //   word's total length taken from the window once; the refill merges the dword
 //   read ahead when 32 bits or fewer are left.
 // merge the dword read ahead when 32 bits or fewer are left (and read the next)
+// NONNEG: nb cannot be negative here (the plain no-run word: its 33 bits hold the word).  A
+// SPLIT word's unary count may run past the window, which leaves nb < 0 for s.slack to report
+// (the group is then replayed): no promise of nb's range there -- with one, the compiler may
+// take every nb for non-negative and drop the slack test that asks for the replay
+template <bool NONNEG = true>
 __device__ __forceinline__ void lmerge(LState &s, const uint8_t *ring) {
     const uint32_t mg = (uint32_t)((s.nb - 33) >> 31);  // ~0: merge
-    const uint32_t sh = (uint32_t)s.nb;
-    __builtin_assume(sh < 64u);
+    uint32_t sh = (uint32_t)s.nb;
+    if constexpr (NONNEG) __builtin_assume(sh < 64u);
+    else sh &= 63u;  // (what the 64-bit shift takes of it anyway)
     s.win |= (uint64_t)(s.nxt & mg) << sh;
     s.nb = mad24((int32_t)mg, -32, s.nb);
     s.ra = ring_step(s.ra, mg);
@@ -993,7 +999,7 @@ __device__ __forceinline__ LW lword_nz(LState &s, const uint8_t *ring, uint32_t 
         s.win >>= q;
         s.nb -= (int32_t)q;
         s.slack = min(s.slack, s.nb);
-        lmerge(s, ring);
+        lmerge<false>(s, ring);
         x = (uint32_t)s.win;
     } else {
         x = __builtin_amdgcn_alignbit(hi, lo, q);
@@ -1190,7 +1196,7 @@ __device__ __forceinline__ void pgroup_try(LState &s, const uint8_t *ring, uint3
         s.rmax = 0u;
         if (__builtin_expect(m26, 0)) {  // (medians below 2^29, none wraps in the group; or hybrid words)
             pgroup<FULL, WK_NORUN_SPLIT32, MONO, HY, CODES>(s, ring, rb, sh, lane, g0, nfr, u0, pfin);
-            lmerge(s, ring);
+            lmerge<false>(s, ring);
             LCNT(cnt.split++);
         } else if (!HY && lmask(mml >= (1u << 17)) == 0ull) {
             if constexpr (WV_LANE_SPEC) s.r0 = (uint32_t)__builtin_ctz(~(uint32_t)s.win | 0x10000u);
@@ -1198,7 +1204,7 @@ __device__ __forceinline__ void pgroup_try(LState &s, const uint8_t *ring, uint3
             LCNT(cnt.norun++);
         } else {
             pgroup<FULL, WK_NORUN_SPLIT, MONO, HY, CODES>(s, ring, rb, sh, lane, g0, nfr, u0, pfin);
-            lmerge(s, ring);  // (the next group's words start from >= 33 bits)
+            lmerge<false>(s, ring);  // (the next group's words start from >= 33 bits)
             LCNT(cnt.split++);
         }
         s.rare = s.rmax >> 4;  // (an escape: the checked words)
