@@ -371,6 +371,60 @@ int wvg_probe_file_md5(const uint8_t *file, size_t len, uint8_t stored[16]);
 /* the kernel's MD5 core (wv_md5.h) run on the host over `len` bytes */
 int wvg_md5_bytes(const uint8_t *data, size_t len, uint8_t digest[16]);
 
+/* ---- Planar float32 on the device (beyond the reference, which has no float output):
+ * the decoded batch as float32 in [-1, 1), channels first, for a model, a resampler or
+ * any DSP on the same device -- one kernel per batch (wv_planar.hip), no download.
+ *   A file is convertible when it opened and is not DSD (a DSD byte holds eight one-bit
+ * samples; decimation is out of scope).  The image holds the convertible files in file
+ * order, file i as C = info.reduced_channels rows (planes) of row_stride floats, row c at
+ * float offset + c * row_stride; with F = info.out_frames:
+ *     fixed_frames == 0 (ragged): row length L = F, row_stride = (F + 3) & ~3, offset =
+ *       the sum of C_j * row_stride_j over the convertible files before it -- every row
+ *       starts at a multiple of 16 bytes from the image's base;
+ *     fixed_frames == T > 0: L = row_stride = T, offset = T * the sum of C_j over the
+ *       convertible files before it -- files of equal C form one dense [B, C, T] array
+ *       (rows are not 16-byte aligned when T % 4 != 0; the kernel does not need them to be).
+ *   Plane c, frame f is conv(out[info.out_offset + f * C + c]) for f < min(F, L); the
+ * frames from min(F, L) to row_stride are +0.0f.  Every float of the image is written by
+ * every call (the destination may be uninitialised memory) and nothing outside it.  What
+ * is converted is whatever the int32 output holds over out_frames, as wvg_batch_format: a
+ * file stopped by an exception has zeros where the decode left zeros.
+ *   conv, by file: (float)v * 2^-k with k = 8 * info.bytes_per_sample - 1 (7, 15, 23, 31;
+ * one-byte samples are signed in the int32 output: no +128), and k = 23 for a float file
+ * decoded without WVG_OPEN_EXACT_FLOAT (the reference's clipped 24-bit integers) whatever
+ * its bytes_per_sample.  The cast rounds to nearest even (it matters above 2^24 only) and
+ * the multiplication by a power of two is exact, so the result is bit for bit numpy's
+ * v.astype(float32) * float32(2.0 ** -k).  A float file decoded under
+ * WVG_OPEN_EXACT_FLOAT holds IEEE-754 patterns already: its 32 bits pass through
+ * unchanged, NaN payloads included (the decision is the framing's, as wvg_batch_md5's
+ * byte form).
+ *   wvg_batch_planar runs after wvg_batch_decode, on `stream` (NULL: the batch's own)
+ * behind the upload and the batch's last decode / format / md5, and returns without
+ * waiting (wvg_batch_sync covers it; the next reset / upload waits for it).  dev_dst ==
+ * NULL: into a buffer the batch owns (cap_floats is ignored), read through
+ * wvg_batch_device_planar / wvg_batch_download_planar until the next such call;
+ * otherwise into the caller's device memory of cap_floats floats on the batch's device
+ * (a torch tensor's data_ptr(), any 4-byte alignment).  Calls with other fixed_frames or
+ * destinations may be queued back to back.  WVG_ERR_SPACE: cap_floats is less than
+ * wvg_batch_planar_floats(b, fixed_frames); WVG_ERR_ARG: before an upload, fixed_frames < 0.
+ *   wvg_batch_file_planar: file i's place in the image -- *frames = min(F, L) -- or
+ * WVG_ERR_OPEN with *offset = -1 for a file that is not convertible (host only, as
+ * wvg_batch_planar_floats; device-framed files are known after the upload).
+ *   wvg_planar_float: the kernel's tile code (wv_planar.h) run on the host over one file's
+ * `frames` x `channels` interleaved ints: `channels` rows of row_stride floats at `out`,
+ * min(frames, row_len) frames converted (kind: 7 / 15 / 23 / 31 = k, 0 = the bits pass
+ * through), +0.0f up to row_stride (>= row_len).  wvg_planar_tile_frames: the frames of one
+ * tile for a channel count (1..255). */
+int wvg_batch_planar(wvg_batch *b, int64_t fixed_frames, float *dev_dst, int64_t cap_floats, void *stream);
+int64_t wvg_batch_planar_floats(const wvg_batch *b, int64_t fixed_frames);
+int wvg_batch_file_planar(const wvg_batch *b, int file, int64_t fixed_frames, int64_t *offset, int64_t *row_stride,
+                          int32_t *channels, int64_t *frames);
+float *wvg_batch_device_planar(wvg_batch *b); /* the batch-owned image of the last dev_dst == NULL call */
+int wvg_batch_download_planar(wvg_batch *b, float *host, int64_t cap_floats); /* that image; waits */
+int wvg_planar_float(const int32_t *src, int64_t frames, int channels, int kind, int64_t row_len, int64_t row_stride,
+                     float *out);
+int wvg_planar_tile_frames(int channels);
+
 /* WvDemo.Main (WvDemo.cs:15-168) for one file of a formatted batch built with
  * chunk_frames 4096: the .wav bytes it writes (stored RIFF header or the
  * synthesized RIFF/fmt/data headers, the PCM, the stored trailer) and its exit

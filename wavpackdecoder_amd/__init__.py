@@ -6,6 +6,7 @@ Layout:
   csrc/wv_decode.hip      HIP kernels for gfx950 (instantiations, lane-per-block PCM/DSD kernels)
   csrc/wv_decode_core.h   per-block decode (host+device source; lane kernels, tests/emu)
   csrc/wv_framing.cpp     host framing: .wv bytes -> block descriptors
+  csrc/wv_planar.h/.hip   planar float32 of a decoded batch (wvg_batch_planar, api.decode_to_tensors)
   csrc/wv_api.cpp         C-ABI (include/wvgpu.h) -> build/libwvgpu.so
   api.py                  mirror of the reference's WavPackUtils API
   shard.py                per-GPU file partition (multi-GPU, no collectives)
@@ -15,6 +16,6 @@ from .api import (  # noqa: F401
     WavpackGetBytesPerSample, WavpackGetErrorMessage, WavpackGetFileFormat, WavpackGetHeader, WavpackGetIsFive,
     WavpackGetIsFloat, WavpackGetMode, WavpackGetNumChannels, WavpackGetNumErrors, WavpackGetNumSamples,
     WavpackGetReducedChannels, WavpackGetSampleIndex, WavpackGetSampleRate, WavpackGetTrailer, WavpackGetVersion,
-    WavpackLossy, WavpackOpenFileInput, WavpackUnpackSamples, wv_demo, SetSample, SetTime,
+    WavpackLossy, WavpackOpenFileInput, WavpackUnpackSamples, wv_demo, SetSample, SetTime, decode_to_tensors,
 )
 from ._lib import build, lib  # noqa: F401

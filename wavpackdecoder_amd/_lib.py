@@ -26,6 +26,7 @@ WVG_ST_REDONE = 0x200  # block status only: decoded by the lane kernel's fallbac
 WVG_ST_UNWRITTEN = 0x40000000  # block status only: no decode stored it since wvg_batch_poison
 WVG_ERR_ARG = -2
 WVG_ERR_OPEN = -3
+WVG_ERR_SPACE = -4
 WVG_ERR_TIMEOUT = -5
 WVG_ERR_EXCEPTION = -6
 WVG_KERNEL_TWO_WAVE = 0
@@ -152,6 +153,14 @@ def lib():
         "wvg_batch_file_streams": (i32, [vp, i32, vp, i32, ctypes.POINTER(ctypes.c_uint32)]),
         "wvg_interleave_streams": (i32, [vp, vp, i32, i64, vp]),
         "wvg_interleave_tile_frames": (i32, [i32]),
+        "wvg_batch_planar": (i32, [vp, i64, vp, i64, vp]),
+        "wvg_batch_planar_floats": (i64, [vp, i64]),
+        "wvg_batch_file_planar": (i32, [vp, i32, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)]),
+        "wvg_batch_device_planar": (vp, [vp]),
+        "wvg_batch_download_planar": (i32, [vp, vp, i64]),
+        "wvg_planar_float": (i32, [vp, i64, i32, i32, i64, i64, vp]),
+        "wvg_planar_tile_frames": (i32, [i32]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -178,6 +187,8 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_batch_device_pcm", "wvg_batch_download_pcm", "wvg_batch_host_pcm", "wvg_batch_download_pcm_async",
             "wvg_batch_wav",
             "wvg_probe_file_streams", "wvg_batch_file_streams", "wvg_interleave_streams", "wvg_interleave_tile_frames",
+            "wvg_batch_planar", "wvg_batch_planar_floats", "wvg_batch_file_planar", "wvg_batch_device_planar",
+            "wvg_batch_download_planar", "wvg_planar_float", "wvg_planar_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of
 # letters and underscores only, so it cannot see a name with a digit in the header and

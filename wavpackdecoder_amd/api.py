@@ -68,16 +68,46 @@ class DecoderTimeout(RuntimeError):
 
 
 _ctx = None
+_ctx_device = -1  # the HIP device of the context (the process's current device when it was opened)
 
 
 def _context():
-    global _ctx
+    global _ctx, _ctx_device
     if _ctx is None:
         L = _L.lib()
         _ctx = L.wvg_open(-1)
         if not _ctx:
             raise RuntimeError("wvg_open failed: no HIP device visible (the decode path is GPU-only)")
+        dev = ctypes.c_int(-1)
+        if L.hipGetDevice(ctypes.byref(dev)) == 0:  # (the HIP runtime libwvgpu.so is linked against)
+            _ctx_device = int(dev.value)
     return _ctx
+
+
+def _torch():
+    """torch, imported lazily (the package works without it), and the check that the process
+    holds one HIP runtime: torch's wheels ship their own libamdhip64, which the loader
+    shares with libwvgpu.so only when torch is imported first.  With two runtimes a
+    tensor's pointer means nothing to the kernels here, so that is an error, not a try."""
+    import torch
+    seen = set()
+    try:
+        with open("/proc/self/maps") as f:
+            for line in f:
+                if "libamdhip64" in line:
+                    seen.add(line.split()[-1])
+    except OSError:
+        pass
+    if len(seen) > 1:
+        raise RuntimeError("two HIP runtimes in this process (" + ", ".join(sorted(seen)) + "): import torch "
+                           "before the first use of wavpackdecoder_amd, so that both share torch's")
+    return torch
+
+
+def context_device() -> int:
+    """The HIP device index every DecodeBatch of this process decodes on."""
+    _context()
+    return _ctx_device
 
 
 def _file_arrays(files):
@@ -100,6 +130,7 @@ class DecodeBatch:
         self.infos: list = []
         self._dev_infos: list = []  # indices of device-framed files (their infos come with the upload)
         self._uploaded = False
+        self._planar_fixed = 0  # fixed_frames of the last planar(out=None)
         self._data: list = []
 
     def add_file(self, data: bytes, open_flags: int = 0, start_sample: int | None = None, wvc: bytes | None = None):
@@ -362,6 +393,67 @@ class DecodeBatch:
         self._check(self._L.wvg_batch_file_md5(self._b, int(i), ctypes.byref(r)))
         return r
 
+    def planar_floats(self, fixed_frames: int = 0) -> int:
+        """Floats of the planar image for fixed_frames (wvg_batch_planar_floats)."""
+        n = int(self._L.wvg_batch_planar_floats(self._b, int(fixed_frames)))
+        if n < 0:
+            raise ValueError("fixed_frames must be >= 0")
+        return n
+
+    def file_planar(self, i: int, fixed_frames: int = 0):
+        """(offset, row_stride, channels, frames) of file i in the planar image
+        (wvg_batch_file_planar); offset -1 for a file that is not convertible (it did not
+        open, or it is DSD)."""
+        off, rs, fr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        ch = ctypes.c_int32()
+        rc = self._L.wvg_batch_file_planar(self._b, int(i), int(fixed_frames), ctypes.byref(off), ctypes.byref(rs),
+                                           ctypes.byref(ch), ctypes.byref(fr))
+        if rc < 0 and rc != _L.WVG_ERR_OPEN:
+            self._check(rc)
+        return int(off.value), int(rs.value), int(ch.value), int(fr.value)
+
+    def planar(self, fixed_frames: int = 0, out=None, stream=None):
+        """The decoded batch as planar float32 in [-1, 1) on the device (wvg_batch_planar;
+        the layout and the conversion: include/wvgpu.h), after decode(), on `stream`, without
+        waiting -- sync() covers it.  fixed_frames 0: every file's rows at their own length
+        (padded to a multiple of 4 floats); T > 0: rows of T frames, cut or zero-padded.
+        out: a contiguous float32 torch tensor on the batch's device with room for
+        planar_floats(fixed_frames) floats, or None for a buffer the batch owns
+        (download_planar, device_planar_ptr).  Returns (offset, row_stride, channels,
+        frames) per file, offset -1 for a file that is not convertible."""
+        if not self._uploaded:
+            self.upload()
+        ptr, cap = None, 0
+        if out is not None:
+            torch = _torch()  # (only a caller that passes a tensor needs it)
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or \
+                    not out.is_contiguous():
+                raise ValueError("out: a contiguous float32 torch tensor on the GPU")
+            if out.device.index != context_device():
+                raise ValueError(f"out is on {out.device}, the batch decodes on device {context_device()}")
+            ptr, cap = ctypes.c_void_p(out.data_ptr()), out.numel()
+        rc = self._L.wvg_batch_planar(self._b, int(fixed_frames), ptr, cap, stream)
+        if rc == _L.WVG_ERR_SPACE:
+            raise ValueError(f"out holds {cap} floats, the image needs {self.planar_floats(fixed_frames)}")
+        if rc == _L.WVG_ERR_ARG and int(fixed_frames) < 0:
+            raise ValueError("fixed_frames must be >= 0")
+        self._check(rc)
+        if out is None:
+            self._planar_fixed = int(fixed_frames)
+        return [self.file_planar(i, fixed_frames) for i in range(len(self.infos))]
+
+    def device_planar_ptr(self) -> int:
+        """Device pointer of the batch-owned planar image (the last planar(out=None))."""
+        return int(self._L.wvg_batch_device_planar(self._b) or 0)
+
+    def download_planar(self) -> np.ndarray:
+        """The batch-owned planar image of the last planar(out=None), as a flat float32
+        array (wvg_batch_download_planar; waits for it)."""
+        n = self.planar_floats(self._planar_fixed)
+        out = np.empty(max(n, 1), dtype=np.float32)
+        self._check(self._L.wvg_batch_download_planar(self._b, out.ctypes.data, out.size))
+        return out[:n]
+
     def wav(self, i: int):
         """WvDemo.Main for file i (WvDemo.cs:15-168): (exit_code, .wav bytes)."""
         n, rc = ctypes.c_int64(), ctypes.c_int32()
@@ -591,6 +683,69 @@ def decode_all_channels(data: bytes, open_flags: int = 0) -> np.ndarray:
         return out[info.out_offset: info.out_offset + n].reshape(-1, info.reduced_channels).copy()
     finally:
         b.close()
+
+
+def planar_tile_frames(channels: int) -> int:
+    """Frames of one tile of the planar-float kernel for a channel count (wv_planar.h)."""
+    t = _L.lib().wvg_planar_tile_frames(int(channels))
+    if t < 0:
+        raise ValueError("channels must be in 1..255")
+    return int(t)
+
+
+def planar_float(src: np.ndarray, kind: int, row_len: int | None = None, row_stride: int | None = None,
+                 out: np.ndarray | None = None) -> np.ndarray:
+    """The planar-float kernel's tile code run on the host (wvg_planar_float): `src` is int32
+    of shape (frames, channels); kind 7 / 15 / 23 / 31 scales by 2^-kind, 0 passes the bits
+    through.  Returns float32 of shape (channels, row_stride) (row_len defaults to frames,
+    row_stride to row_len).  out: a flat float32 array to write into."""
+    a = np.ascontiguousarray(src, dtype=np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    frames, nch = a.shape
+    row_len = frames if row_len is None else int(row_len)
+    row_stride = row_len if row_stride is None else int(row_stride)
+    if out is None:
+        out = np.empty(max(nch * row_stride, 1), dtype=np.float32)
+    rc = _L.lib().wvg_planar_float(a.ctypes.data, frames, nch, int(kind), row_len, row_stride, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_planar_float: {rc}")
+    return out[: nch * row_stride].reshape(nch, row_stride)
+
+
+def decode_to_tensors(files, open_flags: int = 0, fixed_frames: int = 0):
+    """Decode `files` into float32 torch tensors on the GPU, channels first, in [-1, 1):
+    add, upload, decode and planar() on torch's current stream of the batch's device, into
+    one flat tensor, with nothing downloaded.  fixed_frames 0: a list with a [C_i, T_i]
+    view per file, None for a file that is not convertible (it did not open, or it is DSD).
+    fixed_frames T > 0: (tensor [B, C, T], lengths) over the convertible files in file
+    order, every file cut or zero-padded to T frames, lengths[i] = its frames in the
+    tensor; ValueError when their channel counts differ.  Work queued on the same torch
+    stream afterwards sees the tensors complete."""
+    torch = _torch()  # lazily: the package imports without it
+    fixed_frames = int(fixed_frames)
+    if fixed_frames < 0:
+        raise ValueError("fixed_frames must be >= 0")
+    b = DecodeBatch(SAMPLE_BUFFER_SIZE)
+    try:
+        dev = torch.device("cuda", context_device())
+        if len(files):
+            b.add_files(files, open_flags)
+        b.upload()
+        lay = [b.file_planar(i, fixed_frames) for i in range(len(b.infos))]
+        conv = [l for l in lay if l[0] >= 0]
+        if fixed_frames and len({l[2] for l in conv}) > 1:
+            raise ValueError("fixed_frames needs files of one channel count, got " +
+                             str(sorted({l[2] for l in conv})))
+        flat = torch.empty(b.planar_floats(fixed_frames), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        b.decode(stream)
+        b.planar(fixed_frames, out=flat, stream=stream)
+        if fixed_frames:
+            nch = conv[0][2] if conv else 0
+            return flat.view(len(conv), nch, fixed_frames), [l[3] for l in conv]
+        return [None if off < 0 else flat[off: off + ch * rs].view(ch, rs)[:, :fr] for off, rs, ch, fr in lay]
+    finally:
+        b.close()  # (waits for the batch's work: the tensors are complete on return)
 
 
 def verify_files(files, open_flags: int = 0) -> list:

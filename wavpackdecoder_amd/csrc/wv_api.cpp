@@ -20,6 +20,7 @@
 #include "wv_framing.h"
 #include "wv_mc.h"
 #include "wv_md5.h"
+#include "wv_planar.h"
 
 namespace wvg {
 hipError_t launch_decode(const BlockDesc *descs, const uint32_t *pcm_list, uint32_t n_pcm, const uint32_t *dsd_list,
@@ -37,6 +38,7 @@ hipError_t launch_format(const FormatSeg *segs, uint32_t nseg, const int32_t *in
 hipError_t launch_md5(const Md5Job *jobs, uint32_t njobs, const int32_t *out, uint8_t *digests, hipStream_t s);
 hipError_t launch_mc(const McJob *jobs, uint32_t njobs, const McStreamDev *streams, int32_t *out, int plain,
                      hipStream_t s);
+hipError_t launch_planar(const PlJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
 hipError_t launch_zero_fill(const ZeroSeg *segs, uint32_t nseg, int32_t *out, hipStream_t s);
 hipError_t upload_dsd_ptables();
@@ -85,6 +87,7 @@ constexpr double kConcurrentHoldMs = 1000.0;
 // the host for the files the device framer accepts.
 constexpr size_t kDescHead = offsetof(BlockDesc, term) + sizeof(((BlockDesc *)nullptr)->term);
 constexpr int SAMPLE_BUFFER_SIZE = 4096;  // Defines.cs:18, the request size WvDemo uses
+constexpr int kPlTables = 4;  // wvg_batch_planar: job tables (one per fixed_frames value) kept per upload
 constexpr size_t kTimingPending = 64;  // timing pairs left pending before the oldest is folded
 
 struct wvg_batch;
@@ -264,6 +267,29 @@ struct wvg_batch {
     size_t cap_mcjobs = 0, cap_mcstreams = 0;
     uint32_t mc_njobs = 0;
     int mc_plain = 0;  // WVG_MC_PLAIN=1: the strided-store kernel instead of the LDS tile one (A/B)
+    // wvg_batch_planar (wv_planar.h): one job per (convertible file, frame tile).  The jobs
+    // depend on fixed_frames, not on the destination, so a table is built and sent once per
+    // upload and fixed_frames value, into a staging buffer and a device table of its own:
+    // a call queued right behind another never rewrites what the first may still read.
+    // With all kPlTables in use the batch's work is waited for and the oldest is reused.
+    struct PlTable {
+        int64_t fixed = 0, floats = 0;
+        bool valid = false;
+        PinnedBuf stage;
+        PlJob *d_jobs = nullptr;
+        size_t cap = 0;
+        uint32_t njobs = 0;
+    };
+    PlTable pl[kPlTables];
+    int pl_next = 0;
+    float *d_planar = nullptr;  // the batch-owned image (dev_dst == NULL)
+    size_t cap_planar = 0;
+    int64_t planar_floats = -1;  // its floats after the last such call, -1 none since the upload
+    // the image layout of the uploaded files for one fixed_frames value (the per-file
+    // queries of a large batch): offsets per file (-1 not convertible) and the total
+    mutable std::vector<int64_t> pl_off;
+    mutable int64_t pl_lay_fixed = 0, pl_lay_floats = 0;
+    mutable bool pl_lay_valid = false;
 };
 
 static int hip_fail(wvg_ctx *c, hipError_t e, const char *what) {
@@ -286,6 +312,25 @@ static hipError_t ensure(T *&p, size_t &cap, size_t bytes) {
     hipError_t e = hipMalloc(&p, bytes);
     if (e == hipSuccess) cap = bytes;
     return e;
+}
+
+// wvg_batch_planar's jobs (wv_planar.h), the tiles of one file's rows: frames [0, row_stride), the file's own up to `valid`
+template <class F>
+static void pl_file_jobs(uint64_t in_off, uint64_t out_off, uint64_t row_stride, uint64_t valid, uint32_t nch,
+                         uint32_t kind, F &&emit) {
+    const uint64_t tf = pl_tile_frames(nch);
+    for (uint64_t f0 = 0; f0 < row_stride; f0 += tf) {
+        const uint64_t left = row_stride - f0, have = valid > f0 ? valid - f0 : 0;
+        PlJob j;
+        j.in_off = in_off + (have ? f0 * nch : 0);
+        j.out_off = out_off + f0;
+        j.row_stride = row_stride;
+        j.nframes = (uint32_t)(left < tf ? left : tf);
+        j.nvalid = (uint32_t)(have < (uint64_t)j.nframes ? have : j.nframes);
+        j.nch = nch;
+        j.kind = kind;
+        emit(j);
+    }
 }
 
 extern "C" {
@@ -429,6 +474,16 @@ static void free_dev(wvg_batch *b) {
     b->d_mcstreams = nullptr;
     b->cap_mcjobs = b->cap_mcstreams = 0;
     b->mc_njobs = 0;
+    for (auto &t : b->pl) {
+        hipFree(t.d_jobs);
+        t.d_jobs = nullptr;
+        t.cap = 0;
+        t.valid = false;
+    }
+    hipFree(b->d_planar);
+    b->d_planar = nullptr;
+    b->cap_planar = 0;
+    b->planar_floats = -1;
     hipFree(b->d_md5jobs);
     hipFree(b->d_md5);
     b->d_md5jobs = nullptr;
@@ -472,6 +527,15 @@ static hipError_t quiesce(wvg_batch *b) {
         if (e == hipSuccess) e = e2;
     }
     return e;
+}
+
+// The planar job tables and layout belong to one upload (the caller has waited for the
+// batch's work: the tables' buffers are free to be reused).
+static void planar_forget(wvg_batch *b) {
+    for (auto &t : b->pl) t.valid = false;
+    b->pl_next = 0;
+    b->planar_floats = -1;
+    b->pl_lay_valid = false;
 }
 
 // Grow the page-locked blob: a larger one is a new allocation, so a DMA still
@@ -663,6 +727,7 @@ int wvg_batch_reset(wvg_batch *b) {
     b->dev_runs.clear();
     b->framed_dev = b->framed_host = 0;
     b->md5_jobs_sent = b->md5_issued = false;
+    planar_forget(b);
     return WVG_OK;
 }
 
@@ -1188,6 +1253,7 @@ int wvg_batch_upload(wvg_batch *b) {
     const double t_up0 = now_ms();
     b->formatted = false;
     b->md5_jobs_sent = b->md5_issued = false;
+    planar_forget(b);
     // the blob is followed by 64 B of 0xFF (the reader's past-end fill)
     HIPCHK(c, blob_push(b));  // what the adds have not sent yet
     if (!b->d_blob) HIPCHK(c, ensure(b->d_blob, b->cap_blob, 64));
@@ -2078,6 +2144,164 @@ int wvg_probe_file_md5(const uint8_t *file, size_t len, uint8_t stored[16]) {
     if (fi.md5_off < 0) return 0;
     memcpy(stored, file + fi.md5_off, 16);
     return 1;
+}
+
+// ---------------------------------------------------------------------------
+// Planar float32 of the decoded batch on the device (wv_planar.hip)
+// ---------------------------------------------------------------------------
+static bool pl_convertible(const wvg_batch *b, size_t i) {
+    const FileInfo &fi = b->finfo[i];
+    return fi.open_ok && fi.dsd_multiplier == 0 && fi.out_nch >= 1 && fi.out_nch <= (int)kPlMaxChannels &&
+           fi.out_frames >= 0;
+}
+
+static int64_t pl_row_stride(const FileInfo &fi, int64_t fixed) {
+    return fixed > 0 ? fixed : (fi.out_frames + 3) & ~(int64_t)3;
+}
+
+// the image layout for `fixed` (include/wvgpu.h): kept while the batch stays uploaded
+static void pl_layout(const wvg_batch *b, int64_t fixed) {
+    if (b->pl_lay_valid && b->pl_lay_fixed == fixed && b->pl_off.size() == b->finfo.size()) return;
+    b->pl_off.assign(b->finfo.size(), -1);
+    int64_t off = 0;
+    for (size_t i = 0; i < b->finfo.size(); i++) {
+        if (!pl_convertible(b, i)) continue;
+        b->pl_off[i] = off;
+        off += (int64_t)b->finfo[i].out_nch * pl_row_stride(b->finfo[i], fixed);
+    }
+    b->pl_lay_floats = off;
+    b->pl_lay_fixed = fixed;
+    b->pl_lay_valid = b->uploaded;  // (files may still be added to a batch that is not)
+}
+
+int64_t wvg_batch_planar_floats(const wvg_batch *b, int64_t fixed_frames) {
+    if (!b || fixed_frames < 0) return WVG_ERR_ARG;
+    pl_layout(b, fixed_frames);
+    return b->pl_lay_floats;
+}
+
+int wvg_batch_file_planar(const wvg_batch *b, int file, int64_t fixed_frames, int64_t *offset, int64_t *row_stride,
+                          int32_t *channels, int64_t *frames) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || fixed_frames < 0) return WVG_ERR_ARG;
+    pl_layout(b, fixed_frames);
+    const FileInfo &fi = b->finfo[(size_t)file];
+    const bool ok = b->pl_off[(size_t)file] >= 0;
+    const int64_t rs = ok ? pl_row_stride(fi, fixed_frames) : 0;
+    if (offset) *offset = b->pl_off[(size_t)file];
+    if (row_stride) *row_stride = rs;
+    if (channels) *channels = ok ? fi.out_nch : 0;
+    if (frames) *frames = !ok ? 0 : fixed_frames > 0 && fixed_frames < fi.out_frames ? fixed_frames : fi.out_frames;
+    return ok ? WVG_OK : WVG_ERR_OPEN;
+}
+
+// SCALE(k) or the bits of a file's ints (wv_planar.h), from the framing's facts
+static uint32_t pl_kind(const wvg_batch *b, size_t i) {
+    const FileInfo &fi = b->finfo[i];
+    if (fi.is_float) return fi.exact_float ? kPlBits : 23u;
+    const int bps = b->infos[i].bytes_per_sample;
+    return 8u * (uint32_t)(bps < 1 ? 1 : bps > 4 ? 4 : bps) - 1u;
+}
+
+int wvg_batch_planar(wvg_batch *b, int64_t fixed_frames, float *dev_dst, int64_t cap_floats, void *stream) {
+    if (!b || !b->uploaded || fixed_frames < 0) return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    pl_layout(b, fixed_frames);
+    const int64_t floats = b->pl_lay_floats;
+    if (dev_dst && cap_floats < floats) return WVG_ERR_SPACE;
+    wvg_batch::PlTable *t = nullptr;
+    for (auto &x : b->pl)
+        if (x.valid && x.fixed == fixed_frames) t = &x;
+    if (!t) {
+        t = &b->pl[b->pl_next];
+        // a table in use by this upload's earlier calls: they must have finished with it
+        if (t->valid) HIPCHK(c, quiesce(b));
+        t->valid = false;
+        b->pl_next = (b->pl_next + 1) % kPlTables;
+        std::vector<PlJob> jobs;
+        for (size_t i = 0; i < b->finfo.size(); i++) {
+            if (b->pl_off[i] < 0) continue;
+            const FileInfo &fi = b->finfo[i];
+            const uint64_t rs = (uint64_t)pl_row_stride(fi, fixed_frames);
+            const uint64_t valid = (uint64_t)(fi.out_frames < (int64_t)rs ? fi.out_frames : (int64_t)rs);
+            pl_file_jobs((uint64_t)b->infos[i].out_offset, (uint64_t)b->pl_off[i], rs, valid, (uint32_t)fi.out_nch,
+                         pl_kind(b, i), [&](const PlJob &j) { jobs.push_back(j); });
+        }
+        if (jobs.size() > 0x7fffffffu) return WVG_ERR_SPACE;
+        const size_t jb = sizeof(PlJob) * (jobs.empty() ? 1 : jobs.size());
+        // (a grown buffer is a new one; nothing reads this table's: it was invalid since the
+        // upload's wait, or the wait above covered it)
+        if (!t->stage.resize(jb)) return WVG_ERR_SPACE;
+        HIPCHK(c, ensure(t->d_jobs, t->cap, jb));
+        if (!jobs.empty()) {
+            memcpy(t->stage.data(), jobs.data(), sizeof(PlJob) * jobs.size());
+            // on the batch stream, behind the upload's copies; `up` is recorded again so that a
+            // call on a caller's stream waits for the table too (as wvg_batch_md5's jobs)
+            HIPCHK(c, hipMemcpyAsync(t->d_jobs, t->stage.data(), sizeof(PlJob) * jobs.size(), hipMemcpyHostToDevice,
+                                     b->stream));
+            HIPCHK(c, hipEventRecord(b->up, b->stream));
+        }
+        t->njobs = (uint32_t)jobs.size();
+        t->fixed = fixed_frames;
+        t->floats = floats;
+        t->valid = true;
+    }
+    float *dst = dev_dst;
+    if (!dst) {
+        const size_t nb = sizeof(float) * (size_t)(floats ? floats : 1);
+        // (growing frees the old image: an earlier call may still be writing it)
+        if (nb > b->cap_planar && b->d_planar) HIPCHK(c, quiesce(b));
+        HIPCHK(c, ensure(b->d_planar, b->cap_planar, nb));
+        dst = b->d_planar;
+        b->planar_floats = floats;
+    }
+    // after the whole of the last decode, and of whatever ran on the batch since (`done`),
+    // as wvg_batch_format / wvg_batch_md5 order themselves
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_planar(t->d_jobs, t->njobs, b->d_out, dst, s));
+    HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
+    return WVG_OK;
+}
+
+float *wvg_batch_device_planar(wvg_batch *b) { return b && b->planar_floats >= 0 ? b->d_planar : nullptr; }
+
+int wvg_batch_download_planar(wvg_batch *b, float *host, int64_t cap_floats) {
+    if (!b || b->planar_floats < 0 || (!host && b->planar_floats)) return WVG_ERR_ARG;
+    if (cap_floats < b->planar_floats) return WVG_ERR_SPACE;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamWaitEvent(b->stream, b->done, 0));
+    if (b->planar_floats)
+        HIPCHK(c, hipMemcpyAsync(host, b->d_planar, sizeof(float) * (size_t)b->planar_floats, hipMemcpyDeviceToHost,
+                                 b->stream));
+    HIPCHK(c, hipStreamSynchronize(b->stream));
+    return WVG_OK;
+}
+
+int wvg_planar_tile_frames(int channels) {
+    if (channels < 1 || channels > (int)kPlMaxChannels) return WVG_ERR_ARG;
+    return (int)pl_tile_frames((uint32_t)channels);
+}
+
+int wvg_planar_float(const int32_t *src, int64_t frames, int channels, int kind, int64_t row_len, int64_t row_stride,
+                     float *out) {
+    if (channels < 1 || channels > (int)kPlMaxChannels || frames < 0 || row_len < 0 || row_stride < row_len ||
+        (kind != 0 && kind != 7 && kind != 15 && kind != 23 && kind != 31) || (frames && row_len && !src) ||
+        (row_stride && !out))
+        return WVG_ERR_ARG;
+    // the kernel's tile code (wv_planar.h), the workgroup's threads as a loop
+    std::vector<uint32_t> tile(kPlLdsInts + 4, 0u);
+    uint32_t *t = tile.data();
+    while ((uintptr_t)t & 15u) t++;
+    pl_file_jobs(0, 0, (uint64_t)row_stride, (uint64_t)(frames < row_len ? frames : row_len), (uint32_t)channels,
+                 (uint32_t)kind, [&](const PlJob &j) {
+                     for (uint32_t tid = 0; tid < kPlThreads; tid++)
+                         pl_load(j, src + j.in_off, out + j.out_off, t, tid, kPlThreads);
+                     for (uint32_t tid = 0; tid < kPlThreads; tid++) pl_store(j, t, out + j.out_off, tid, kPlThreads);
+                 });
+    return WVG_OK;
 }
 
 // ---- multichannel files (WVG_OPEN_ALL_CHANNELS) ----

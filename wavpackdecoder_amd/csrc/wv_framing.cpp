@@ -1571,6 +1571,7 @@ static void frame_one(const uint8_t *file, size_t len, uint64_t blob_base, uint6
     // with sent bits its wvx stream.
     const bool xf = F.exact_float && info.is_float;
     info.md5_bps = xf ? 4 : info.bytes_per_sample;
+    info.exact_float = xf;
     bool cmp = seek_to < 0 && (F.reduced_channels == 0 || sel >= 0);
     for (int64_t k = info.first_desc; cmp && k < info.first_desc + info.num_desc; k++) {
         const BlockDesc &d = out.descs[(size_t)k];

@@ -61,6 +61,9 @@ struct FileInfo {
     // channels), md5_bps bytes a value.
     int64_t md5_off = -1;
     int32_t md5_comparable = 0, md5_bps = 0;
+    // a float file under OPEN_EXACT_FLOAT: its output ints are float32 bit patterns (the
+    // fact behind md5_bps = 4; wvg_batch_planar passes them through)
+    int32_t exact_float = 0;
     // blocks of this file inside the batch descriptor array
     int64_t first_desc = 0, num_desc = 0;
     // OPEN_ALL_CHANNELS on a file of more than two channels: its streams (empty otherwise;
