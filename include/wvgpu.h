@@ -425,6 +425,58 @@ int wvg_planar_float(const int32_t *src, int64_t frames, int channels, int kind,
                      float *out);
 int wvg_planar_tile_frames(int channels);
 
+/* ---- Per-channel level statistics on the device (beyond the reference): what a consumer
+ * of a decoded batch computes next -- peak, DC offset, RMS, clip count, where the audio
+ * starts and ends -- as exact integers, 64 bytes per channel, with two kernels per batch
+ * (wv_levels.hip) and no PCM downloaded: the statistics twin of wvg_batch_md5.
+ *   A file is measurable when it opened, is not DSD (a DSD byte holds eight one-bit
+ * samples) and is not a float file decoded under WVG_OPEN_EXACT_FLOAT (its ints are
+ * IEEE-754 patterns, and sums of floats are not exact).  Measured is whatever the int32
+ * output holds over info.out_frames frames of C = info.reduced_channels interleaved ints at
+ * info.out_offset, as wvg_batch_format, md5 and planar: a file stopped by an exception has
+ * its zeros counted, a WVG_OPEN_ALL_CHANNELS file is measured over its woven N channels.
+ *   One record per channel, over the channel's values v:
+ *     min, max      0, 0 for a file of no frames
+ *     sum           exact
+ *     sumsq         the sum of v * v as a 128-bit integer, sumsq_hi * 2^64 + sumsq_lo, exact
+ *     clipped       values on the rails: v >= 2^k - 1 or v <= -2^k
+ *     active        values with v > thr or v < -thr
+ *     first_active, last_active   frame index of the first / last active value, -1: none
+ * k is planar's full-scale exponent: 8 * info.bytes_per_sample - 1 (7, 15, 23, 31), and 23
+ * for a float file decoded without WVG_OPEN_EXACT_FLOAT.  thr = threshold_q31 >> (31 - k):
+ * one silence threshold in Q31 full-scale units, applied by each file at its own depth.
+ * INT32_MIN is a legal value of 32-bit files; no absolute value is taken anywhere.
+ *   wvg_batch_levels runs after wvg_batch_decode, on `stream` (NULL: the batch's own)
+ * behind the upload and the batch's last decode / format / md5 / planar / levels, and
+ * returns without waiting (wvg_batch_sync covers it; the next reset / upload waits for
+ * it).  The records come down with the call, queued behind the kernels into page-locked
+ * memory.  Calls with other thresholds may be queued back to back: each starts on the
+ * device when the one before has downloaded its records, and the last one defines what
+ * wvg_batch_file_levels returns.  Every record is written by every call.  WVG_ERR_ARG:
+ * before an upload, threshold_q31 above 0x7FFFFFFF.
+ *   wvg_batch_file_levels, after wvg_batch_sync: returns C and fills min(C, cap_channels)
+ * records; WVG_ERR_OPEN for a file that is not measurable; WVG_ERR_ARG when no
+ * wvg_batch_levels ran since the last upload.
+ *   wvg_levels_ints: the kernels' tile and combine code (wv_levels.h) run on the host over
+ * `frames` x `channels` interleaved ints (channels 1..255, k one of 7 / 15 / 23 / 31):
+ * `channels` records at `out`.  wvg_levels_tile_frames: the frames of one tile for a channel
+ * count (1..255). */
+typedef struct {            /* 64 bytes, one per (measurable file, channel) */
+    int32_t  min, max;
+    int64_t  sum;
+    uint64_t sumsq_lo, sumsq_hi;
+    int64_t  clipped;
+    int64_t  active;
+    int64_t  first_active;
+    int64_t  last_active;
+} wvg_channel_levels;
+
+int wvg_batch_levels(wvg_batch *b, uint32_t threshold_q31, void *stream);
+int wvg_batch_file_levels(wvg_batch *b, int file, wvg_channel_levels *out, int cap_channels);
+int wvg_levels_ints(const int32_t *src, int64_t frames, int channels, int k, uint32_t threshold_q31,
+                    wvg_channel_levels *out);
+int wvg_levels_tile_frames(int channels);
+
 /* WvDemo.Main (WvDemo.cs:15-168) for one file of a formatted batch built with
  * chunk_frames 4096: the .wav bytes it writes (stored RIFF header or the
  * synthesized RIFF/fmt/data headers, the PCM, the stored trailer) and its exit

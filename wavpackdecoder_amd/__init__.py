@@ -7,6 +7,7 @@ Layout:
   csrc/wv_decode_core.h   per-block decode (host+device source; lane kernels, tests/emu)
   csrc/wv_framing.cpp     host framing: .wv bytes -> block descriptors
   csrc/wv_planar.h/.hip   planar float32 of a decoded batch (wvg_batch_planar, api.decode_to_tensors)
+  csrc/wv_levels.h/.hip   per-channel level statistics of a decoded batch (wvg_batch_levels, api.scan_levels)
   csrc/wv_api.cpp         C-ABI (include/wvgpu.h) -> build/libwvgpu.so
   api.py                  mirror of the reference's WavPackUtils API
   shard.py                per-GPU file partition (multi-GPU, no collectives)
@@ -17,5 +18,6 @@ from .api import (  # noqa: F401
     WavpackGetIsFloat, WavpackGetMode, WavpackGetNumChannels, WavpackGetNumErrors, WavpackGetNumSamples,
     WavpackGetReducedChannels, WavpackGetSampleIndex, WavpackGetSampleRate, WavpackGetTrailer, WavpackGetVersion,
     WavpackLossy, WavpackOpenFileInput, WavpackUnpackSamples, wv_demo, SetSample, SetTime, decode_to_tensors,
+    scan_levels,
 )
 from ._lib import build, lib  # noqa: F401

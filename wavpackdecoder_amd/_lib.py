@@ -58,6 +58,11 @@ class WvgFileMd5(ctypes.Structure):
     ]
 
 
+# wvg_channel_levels (include/wvgpu.h): one 64-byte record per (measurable file, channel)
+LEVELS_DTYPE = [("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("sumsq_lo", "<u8"), ("sumsq_hi", "<u8"),
+                ("clipped", "<i8"), ("active", "<i8"), ("first_active", "<i8"), ("last_active", "<i8")]
+
+
 class WvgFileResult(ctypes.Structure):
     _fields_ = [
         ("frames", ctypes.c_int64), ("crc_errors", ctypes.c_int64), ("lossy", ctypes.c_int32),
@@ -161,6 +166,10 @@ def lib():
         "wvg_batch_download_planar": (i32, [vp, vp, i64]),
         "wvg_planar_float": (i32, [vp, i64, i32, i32, i64, i64, vp]),
         "wvg_planar_tile_frames": (i32, [i32]),
+        "wvg_batch_levels": (i32, [vp, u32, vp]),
+        "wvg_batch_file_levels": (i32, [vp, i32, vp, i32]),
+        "wvg_levels_ints": (i32, [vp, i64, i32, i32, u32, vp]),
+        "wvg_levels_tile_frames": (i32, [i32]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -189,6 +198,7 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_probe_file_streams", "wvg_batch_file_streams", "wvg_interleave_streams", "wvg_interleave_tile_frames",
             "wvg_batch_planar", "wvg_batch_planar_floats", "wvg_batch_file_planar", "wvg_batch_device_planar",
             "wvg_batch_download_planar", "wvg_planar_float", "wvg_planar_tile_frames",
+            "wvg_batch_levels", "wvg_batch_file_levels", "wvg_levels_ints", "wvg_levels_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of
 # letters and underscores only, so it cannot see a name with a digit in the header and

@@ -27,6 +27,7 @@ For throughput use DecodeBatch: many files, one upload, one decode.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -454,6 +455,34 @@ class DecodeBatch:
         self._check(self._L.wvg_batch_download_planar(self._b, out.ctypes.data, out.size))
         return out[:n]
 
+    def levels(self, threshold_q31: int = 0, stream=None):
+        """Every measurable file's per-channel level statistics on the device
+        (wvg_batch_levels; the fields: include/wvgpu.h), after decode(), on `stream`, without
+        waiting -- sync() covers it.  threshold_q31: the silence threshold in Q31 full-scale
+        units (0 .. 0x7FFFFFFF), shifted down to each file's depth."""
+        threshold_q31 = int(threshold_q31)
+        if not 0 <= threshold_q31 <= 0x7FFFFFFF:
+            raise ValueError("threshold_q31 must be in 0..0x7FFFFFFF")
+        if not self._uploaded:
+            self.upload()
+        self._check(self._L.wvg_batch_levels(self._b, threshold_q31, stream))
+
+    def file_levels(self, i: int):
+        """File i's records of the last levels() (wvg_batch_file_levels; after sync()): a
+        structured array (_lib.LEVELS_DTYPE) of one record per channel, or None for a file
+        that is not measurable (it did not open, it is DSD, or it is a float file decoded
+        under OPEN_EXACT_FLOAT)."""
+        n = self._L.wvg_batch_file_levels(self._b, int(i), None, 0)
+        if n == _L.WVG_ERR_OPEN:
+            return None
+        if n < 0:
+            self._check(n)
+        out = np.zeros(n, dtype=_L.LEVELS_DTYPE)
+        got = self._L.wvg_batch_file_levels(self._b, int(i), out.ctypes.data, n)
+        if got != n:
+            self._check(got if got < 0 else _L.WVG_ERR_ARG)
+        return out
+
     def wav(self, i: int):
         """WvDemo.Main for file i (WvDemo.cs:15-168): (exit_code, .wav bytes)."""
         n, rc = ctypes.c_int64(), ctypes.c_int32()
@@ -762,6 +791,81 @@ def verify_files(files, open_flags: int = 0) -> list:
         b.md5()
         b.sync()
         return [b.file_md5(i) if i >= 0 else None for i in idx]
+    finally:
+        b.close()
+
+
+def levels_tile_frames(channels: int) -> int:
+    """Frames of one tile of the levels kernel for a channel count (wv_levels.h)."""
+    t = _L.lib().wvg_levels_tile_frames(int(channels))
+    if t < 0:
+        raise ValueError("channels must be in 1..255")
+    return int(t)
+
+
+def levels_ints(src: np.ndarray, k: int, threshold_q31: int = 0) -> np.ndarray:
+    """The levels kernels' tile and combine code run on the host (wvg_levels_ints): `src` is
+    int32 of shape (frames, channels) -- any int alignment -- and full scale is 2^k (k 7 /
+    15 / 23 / 31).  Returns one record (_lib.LEVELS_DTYPE) per channel."""
+    a = np.asarray(src)
+    if a.dtype != np.int32:
+        a = a.astype(np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    if not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    frames, nch = a.shape
+    threshold_q31 = int(threshold_q31)
+    if not 0 <= threshold_q31 <= 0xFFFFFFFF:
+        raise ValueError("threshold_q31 must be in 0..0x7FFFFFFF")
+    out = np.zeros(max(nch, 1), dtype=_L.LEVELS_DTYPE)
+    rc = _L.lib().wvg_levels_ints(a.ctypes.data, frames, nch, int(k), threshold_q31, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_levels_ints: {rc}")
+    return out[:nch]
+
+
+def _dbfs(x: float) -> float:
+    return 20.0 * math.log10(x) if x > 0 else float("-inf")
+
+
+def scan_levels(files, open_flags: int = 0, threshold_q31: int = 0) -> list:
+    """Decode `files` and measure each channel's levels on the device: add, upload, decode,
+    levels and sync, with no PCM formatted or downloaded (64 bytes a channel come back).
+    Returns one dict per file, None for a file that is not measurable:
+      records     the structured array of DecodeBatch.file_levels (exact integers)
+      sumsq       per channel, sumsq_hi * 2^64 + sumsq_lo as a Python int
+      k           full scale is 2^k
+      out_frames  the frames measured
+      peak_dbfs, rms_dbfs, dc   per channel, Python floats relative to full scale
+                  (max(|min|, |max|) / 2^k and sqrt(sumsq / frames) / 2^k in dB, -inf for
+                  silence; sum / frames / 2^k)
+    The last three are conveniences derived here in floating point; they are not part of
+    the exact contract the records keep."""
+    if not len(files):
+        return []
+    b = DecodeBatch(SAMPLE_BUFFER_SIZE)
+    try:
+        idx = b.add_files(files, open_flags)
+        b.decode()
+        b.levels(threshold_q31)
+        b.sync()
+        res = []
+        for i in idx:
+            rec = b.file_levels(i) if i >= 0 else None
+            if rec is None:
+                res.append(None)
+                continue
+            info = b.infos[i]
+            k = 23 if info.is_float else 8 * min(max(int(info.bytes_per_sample), 1), 4) - 1
+            n, fs = int(info.out_frames), float(1 << k)
+            sumsq = [(int(r["sumsq_hi"]) << 64) | int(r["sumsq_lo"]) for r in rec]
+            res.append({
+                "records": rec, "sumsq": sumsq, "k": k, "out_frames": n,
+                "peak_dbfs": [_dbfs(max(-int(r["min"]), int(r["max"])) / fs) for r in rec],
+                "rms_dbfs": [_dbfs(math.sqrt(q / n) / fs) if n else float("-inf") for q in sumsq],
+                "dc": [int(r["sum"]) / n / fs if n else 0.0 for r in rec],
+            })
+        return res
     finally:
         b.close()
 

@@ -18,6 +18,7 @@
 #include "wv_desc.h"
 #include "wv_format.h"
 #include "wv_framing.h"
+#include "wv_levels.h"
 #include "wv_mc.h"
 #include "wv_md5.h"
 #include "wv_planar.h"
@@ -39,6 +40,8 @@ hipError_t launch_md5(const Md5Job *jobs, uint32_t njobs, const int32_t *out, ui
 hipError_t launch_mc(const McJob *jobs, uint32_t njobs, const McStreamDev *streams, int32_t *out, int plain,
                      hipStream_t s);
 hipError_t launch_planar(const PlJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
+hipError_t launch_levels(const LvJob *jobs, uint32_t njobs, const LvFold *folds, uint32_t nfolds, const int32_t *in,
+                         LvRecord *partials, LvRecord *out, uint32_t threshold_q31, hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
 hipError_t launch_zero_fill(const ZeroSeg *segs, uint32_t nseg, int32_t *out, hipStream_t s);
 hipError_t upload_dsd_ptables();
@@ -290,6 +293,20 @@ struct wvg_batch {
     mutable std::vector<int64_t> pl_off;
     mutable int64_t pl_lay_fixed = 0, pl_lay_floats = 0;
     mutable bool pl_lay_valid = false;
+    // wvg_batch_levels (wv_levels.h): one job per (measurable file, frame tile) and one fold
+    // per (measurable file, channel), built and sent once per upload.  The threshold is a
+    // kernel argument, so calls with other thresholds share the tables.  They share the
+    // partials, the records and their page-locked landing area too: every call waits for
+    // `done` and records it behind its download, so a later call starts on the device
+    // only when the one before has finished with all three.
+    LvJob *d_lvjobs = nullptr;
+    LvFold *d_lvfolds = nullptr;
+    LvRecord *d_lvpart = nullptr, *d_levels = nullptr;
+    size_t cap_lvjobs = 0, cap_lvfolds = 0, cap_lvpart = 0, cap_levels = 0;
+    PinnedBuf lv_stage, hlevels;
+    std::vector<int64_t> lv_rec0;  // per file: its channel-0 record, -1 not measurable
+    uint32_t lv_njobs = 0, lv_nfolds = 0;
+    bool lv_jobs_sent = false, lv_issued = false;
 };
 
 static int hip_fail(wvg_ctx *c, hipError_t e, const char *what) {
@@ -331,6 +348,33 @@ static void pl_file_jobs(uint64_t in_off, uint64_t out_off, uint64_t row_stride,
         j.kind = kind;
         emit(j);
     }
+}
+
+// the tiles of one file (wv_levels.h) and its folds; `part`: its first record in the partials
+template <class J, class F>
+static uint64_t lv_file_jobs(uint64_t in_off, uint64_t frames, uint32_t nch, uint32_t k, uint64_t part, J &&job,
+                             F &&fold) {
+    const uint64_t tf = lv_tile_frames(nch), ntiles = (frames + tf - 1) / tf;
+    for (uint64_t t = 0; t < ntiles; t++) {
+        const uint64_t f0 = t * tf, left = frames - f0;
+        LvJob j;
+        j.in_off = in_off + f0 * nch;
+        j.frame0 = f0;
+        j.part = part + t * nch;
+        j.nvalid = (uint32_t)(left < tf ? left : tf);
+        j.nch = nch;
+        j.k = k;
+        j.pad_ = 0;
+        job(j);
+    }
+    for (uint32_t c = 0; c < nch; c++) {
+        LvFold f;
+        f.part = part + c;
+        f.ntiles = (uint32_t)ntiles;
+        f.nch = nch;
+        fold(f);
+    }
+    return part + ntiles * nch;
 }
 
 extern "C" {
@@ -484,6 +528,15 @@ static void free_dev(wvg_batch *b) {
     b->d_planar = nullptr;
     b->cap_planar = 0;
     b->planar_floats = -1;
+    hipFree(b->d_lvjobs);
+    hipFree(b->d_lvfolds);
+    hipFree(b->d_lvpart);
+    hipFree(b->d_levels);
+    b->d_lvjobs = nullptr;
+    b->d_lvfolds = nullptr;
+    b->d_lvpart = b->d_levels = nullptr;
+    b->cap_lvjobs = b->cap_lvfolds = b->cap_lvpart = b->cap_levels = 0;
+    b->lv_jobs_sent = b->lv_issued = false;
     hipFree(b->d_md5jobs);
     hipFree(b->d_md5);
     b->d_md5jobs = nullptr;
@@ -727,6 +780,7 @@ int wvg_batch_reset(wvg_batch *b) {
     b->dev_runs.clear();
     b->framed_dev = b->framed_host = 0;
     b->md5_jobs_sent = b->md5_issued = false;
+    b->lv_jobs_sent = b->lv_issued = false;
     planar_forget(b);
     return WVG_OK;
 }
@@ -1253,6 +1307,7 @@ int wvg_batch_upload(wvg_batch *b) {
     const double t_up0 = now_ms();
     b->formatted = false;
     b->md5_jobs_sent = b->md5_issued = false;
+    b->lv_jobs_sent = b->lv_issued = false;
     planar_forget(b);
     // the blob is followed by 64 B of 0xFF (the reader's past-end fill)
     HIPCHK(c, blob_push(b));  // what the adds have not sent yet
@@ -2301,6 +2356,147 @@ int wvg_planar_float(const int32_t *src, int64_t frames, int channels, int kind,
                          pl_load(j, src + j.in_off, out + j.out_off, t, tid, kPlThreads);
                      for (uint32_t tid = 0; tid < kPlThreads; tid++) pl_store(j, t, out + j.out_off, tid, kPlThreads);
                  });
+    return WVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Per-channel level statistics of the decoded batch on the device (wv_levels.hip)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(wvg_channel_levels) == 64 && sizeof(LvRecord) == 64, "one record is 64 bytes");
+static_assert(offsetof(wvg_channel_levels, max) == offsetof(LvRecord, max) &&
+                  offsetof(wvg_channel_levels, sum) == offsetof(LvRecord, sum) &&
+                  offsetof(wvg_channel_levels, sumsq_lo) == offsetof(LvRecord, sumsq_lo) &&
+                  offsetof(wvg_channel_levels, sumsq_hi) == offsetof(LvRecord, sumsq_hi) &&
+                  offsetof(wvg_channel_levels, clipped) == offsetof(LvRecord, clipped) &&
+                  offsetof(wvg_channel_levels, active) == offsetof(LvRecord, active) &&
+                  offsetof(wvg_channel_levels, first_active) == offsetof(LvRecord, first_active) &&
+                  offsetof(wvg_channel_levels, last_active) == offsetof(LvRecord, last_active),
+              "LvRecord is wvg_channel_levels");
+
+// integers whose sums are exact: not DSD, not the IEEE patterns of an exact-float decode
+static bool lv_measurable(const wvg_batch *b, size_t i) {
+    const FileInfo &fi = b->finfo[i];
+    return pl_convertible(b, i) && !(fi.is_float && fi.exact_float);
+}
+
+int wvg_batch_levels(wvg_batch *b, uint32_t threshold_q31, void *stream) {
+    if (!b || !b->uploaded || threshold_q31 > 0x7FFFFFFFu) return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    const size_t nf = b->finfo.size();
+    if (!b->lv_jobs_sent) {
+        std::vector<LvJob> jobs;
+        std::vector<LvFold> folds;
+        b->lv_rec0.assign(nf, -1);
+        uint64_t part = 0;
+        for (size_t i = 0; i < nf; i++) {
+            if (!lv_measurable(b, i)) continue;
+            const FileInfo &fi = b->finfo[i];
+            if ((uint64_t)fi.out_frames / lv_tile_frames((uint32_t)fi.out_nch) >= 0x7fffffffu) return WVG_ERR_SPACE;
+            b->lv_rec0[i] = (int64_t)folds.size();
+            part = lv_file_jobs((uint64_t)b->infos[i].out_offset, (uint64_t)fi.out_frames, (uint32_t)fi.out_nch,
+                                pl_kind(b, i), part, [&](const LvJob &j) { jobs.push_back(j); },
+                                [&](const LvFold &f) { folds.push_back(f); });
+        }
+        if (jobs.size() > 0x7fffffffu || folds.size() > 0x7fffffffu) return WVG_ERR_SPACE;
+        // (the buffers below may still be in use by a call of the previous upload only
+        // through a caller's stream: the upload's quiesce waited for it)
+        const size_t jb = sizeof(LvJob) * jobs.size(), fb = sizeof(LvFold) * folds.size();
+        const size_t rb = sizeof(LvRecord) * (folds.size() ? folds.size() : 1);
+        if (!b->lv_stage.resize(jb + fb + 1) || !b->hlevels.resize(rb)) return WVG_ERR_SPACE;
+        HIPCHK(c, ensure(b->d_lvjobs, b->cap_lvjobs, jb ? jb : 1));
+        HIPCHK(c, ensure(b->d_lvfolds, b->cap_lvfolds, fb ? fb : 1));
+        HIPCHK(c, ensure(b->d_lvpart, b->cap_lvpart, sizeof(LvRecord) * (size_t)(part ? part : 1)));
+        HIPCHK(c, ensure(b->d_levels, b->cap_levels, rb));
+        // on the batch stream, behind the upload's copies; `up` is recorded again so that a
+        // call on a caller's stream waits for the tables too (as wvg_batch_md5's jobs)
+        if (jb) {
+            memcpy(b->lv_stage.data(), jobs.data(), jb);
+            HIPCHK(c, hipMemcpyAsync(b->d_lvjobs, b->lv_stage.data(), jb, hipMemcpyHostToDevice, b->stream));
+        }
+        if (fb) {
+            memcpy(b->lv_stage.data() + jb, folds.data(), fb);
+            HIPCHK(c, hipMemcpyAsync(b->d_lvfolds, b->lv_stage.data() + jb, fb, hipMemcpyHostToDevice, b->stream));
+        }
+        HIPCHK(c, hipEventRecord(b->up, b->stream));
+        b->lv_njobs = (uint32_t)jobs.size();
+        b->lv_nfolds = (uint32_t)folds.size();
+        b->lv_jobs_sent = true;
+    }
+    // after the whole of the last decode, and of whatever ran on the batch since (`done`):
+    // an earlier wvg_batch_levels has then downloaded its records, so this one may rewrite them
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_levels(b->d_lvjobs, b->lv_njobs, b->d_lvfolds, b->lv_nfolds, b->d_out, b->d_lvpart, b->d_levels,
+                            threshold_q31, s));
+    if (b->lv_nfolds)
+        HIPCHK(c, hipMemcpyAsync(b->hlevels.data(), b->d_levels, sizeof(LvRecord) * (size_t)b->lv_nfolds,
+                                 hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
+    b->lv_issued = true;
+    return WVG_OK;
+}
+
+int wvg_batch_file_levels(wvg_batch *b, int file, wvg_channel_levels *out, int cap_channels) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || cap_channels < 0 || (cap_channels && !out) || !b->lv_issued)
+        return WVG_ERR_ARG;
+    const int64_t r0 = b->lv_rec0[(size_t)file];
+    if (r0 < 0) return WVG_ERR_OPEN;
+    const int nch = b->finfo[(size_t)file].out_nch, n = nch < cap_channels ? nch : cap_channels;
+    if (n > 0) memcpy(out, b->hlevels.data() + sizeof(LvRecord) * (size_t)r0, sizeof(LvRecord) * (size_t)n);
+    return nch;
+}
+
+int wvg_levels_tile_frames(int channels) {
+    if (channels < 1 || channels > (int)kLvMaxChannels) return WVG_ERR_ARG;
+    return (int)lv_tile_frames((uint32_t)channels);
+}
+
+int wvg_levels_ints(const int32_t *src, int64_t frames, int channels, int k, uint32_t threshold_q31,
+                    wvg_channel_levels *out) {
+    if (channels < 1 || channels > (int)kLvMaxChannels || frames < 0 || (k != 7 && k != 15 && k != 23 && k != 31) ||
+        threshold_q31 > 0x7FFFFFFFu || (frames && !src) || !out)
+        return WVG_ERR_ARG;
+    // the kernels' code (wv_levels.h), the workgroup's threads as loops
+    std::vector<LvJob> jobs;
+    std::vector<LvFold> folds;
+    const uint64_t nparts = lv_file_jobs(0, (uint64_t)frames, (uint32_t)channels, (uint32_t)k, 0,
+                                         [&](const LvJob &j) { jobs.push_back(j); },
+                                         [&](const LvFold &f) { folds.push_back(f); });
+    std::vector<LvRecord> partials((size_t)nparts);
+    std::vector<int32_t> tile(kLvLdsInts);
+    std::vector<LvAcc> acc(kLvThreads), nxt(kLvThreads);
+    for (const LvJob &j : jobs) {
+        for (uint32_t tid = 0; tid < kLvThreads; tid++) lv_load(j, src + j.in_off, tile.data(), tid, kLvThreads);
+        for (uint32_t tid = 0; tid < kLvThreads; tid++) acc[tid] = lv_scan(j, tile.data(), tid, threshold_q31);
+        const uint32_t lanes = lv_tree_lanes(j.nch), waves = lv_row_waves(j.nch), segs = lv_segments(j.nch);
+        for (uint32_t m = kLvWave / 2; m; m >>= 1) {
+            if (lanes <= m) continue;
+            for (uint32_t tid = 0; tid < kLvThreads; tid++) nxt[tid] = lv_merge(acc[tid], acc[tid ^ m]);
+            acc.swap(nxt);
+        }
+        for (uint32_t tid = 0; tid < kLvThreads; tid++) {
+            if (waves > 1u) {
+                if (tid >= j.nch) continue;
+                LvAcc a = acc[tid * waves * kLvWave];
+                for (uint32_t w = 1; w < waves; w++) a = lv_merge(a, acc[(tid * waves + w) * kLvWave]);
+                lv_partial(j, a, partials.data() + j.part + tid);
+            } else {
+                const uint32_t c = tid / segs;
+                if (c < j.nch && tid == c * segs) lv_partial(j, acc[tid], partials.data() + j.part + c);
+            }
+        }
+    }
+    std::vector<LvRecord> lane(kLvCombineLanes), lnxt(kLvCombineLanes);
+    for (size_t r = 0; r < folds.size(); r++) {
+        for (uint32_t l = 0; l < kLvCombineLanes; l++) lane[l] = lv_fold(folds[r], partials.data(), l, kLvCombineLanes);
+        for (uint32_t m = kLvCombineLanes / 2; m; m >>= 1) {
+            for (uint32_t l = 0; l < kLvCombineLanes; l++) lnxt[l] = lv_rec_merge(lane[l], lane[l ^ m]);
+            lane.swap(lnxt);
+        }
+        lv_final(folds[r], lane[0], reinterpret_cast<LvRecord *>(out) + r);
+    }
     return WVG_OK;
 }
 
