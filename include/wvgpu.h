@@ -425,6 +425,73 @@ int wvg_planar_float(const int32_t *src, int64_t frames, int channels, int kind,
                      float *out);
 int wvg_planar_tile_frames(int channels);
 
+/* ---- Planar float32 at one sample rate on the device (beyond the reference): planar's
+ * twin.  After a decode every resamplable file is converted as above and brought from its
+ * own info.sample_rate to the caller's out_rate by a polyphase FIR, float32 and channels
+ * first in planar's two layouts -- one kernel per batch (wv_resample.hip) plus the uploads
+ * of the filter tables, no download.  With fixed_frames files of one channel count form one
+ * dense [B, C, T] array at one rate.
+ *   Rates: g = gcd(in_rate, out_rate), orig = in_rate / g, new = out_rate / g.  The pair is
+ * supported when orig <= 1024, new <= 1024 and K <= 4096 (K below).
+ *   Filter: a Hann-windowed sinc in the layout of torchaudio's sinc_interp_hann resampler,
+ * with fixed parameters lpw = 6 zero crossings and rolloff = 0.99, in float64 on the host:
+ *     base  = min(orig, new) * rolloff
+ *     width = ceil(lpw * orig / base)          K = 2 * width + orig
+ *     for p in 0..new-1, j in 0..K-1:
+ *         t = clamp((-p / new + (j - width) / orig) * base, -lpw, +lpw)
+ *         h64[p][j] = sinc(pi * t) * cos(pi * t / (2 * lpw))^2 * (base / orig)     (sinc(0) = 1)
+ *         h[p][j]   = +0.0f if |h64| < 2^-64 else (float)h64     (one rounding, to nearest even)
+ * (the flush keeps every product away from float32 denormals: host and device cannot
+ * differ by a denormal mode).
+ *   Output: with F = info.out_frames and x[c][m] = planar's conv(out[out_offset + m * C + c])
+ * for 0 <= m < F (SCALE(k), the same k rule), else +0.0f, the file has
+ * F' = ceil(F * new / orig) output frames, and for n = i * new + p with 0 <= p < new
+ *     y[c][n] = acc_K,  acc_0 = +0.0f,  acc_{j+1} = fmaf(h[p][j], x[c][i * orig + j - width], acc_j)
+ * with j = 0 .. K-1 ascending: one accumulator, one order, fused multiply-adds.  A tap
+ * outside the file adds exactly nothing.  in_rate == out_rate: no filter; the row is
+ * planar's conversion bit for bit.
+ *   A file is resamplable when it opened, is not DSD, is not a float file decoded under
+ * WVG_OPEN_EXACT_FLOAT (levels' rule: use the default clipped 24-bit decode), has
+ * sample_rate > 0, and its pair is supported.  The others take no room in the image: their
+ * offset is -1 and wvg_batch_file_resample returns WVG_ERR_OPEN.  WVG_OPEN_ALL_CHANNELS
+ * files are resampled over their woven N channels, 1 to 255.
+ *   Image: planar's rules with F' in place of F -- ragged: row length F', row_stride =
+ * (F' + 3) & ~3; fixed_frames == T > 0: rows of T output-rate frames, cut or zero-padded.
+ * Every float of the image is written by every call and nothing outside it; the
+ * destination is at any 4-byte alignment; all offsets are 64-bit.
+ *   wvg_batch_resample is ordered as wvg_batch_planar: after wvg_batch_decode, on `stream`
+ * (NULL: the batch's own) behind the upload and the batch's last decode / format / md5 /
+ * planar / levels / resample; it returns without waiting, and wvg_batch_sync, reset and
+ * upload cover it.  dev_dst == NULL: into a buffer the batch owns, its own and not
+ * planar's (wvg_batch_device_resampled / wvg_batch_download_resampled until the next such
+ * call).  Job tables are built once per upload and (out_rate, fixed_frames), filter tables
+ * once per batch and (in_rate, out_rate), each into memory of its own, so calls with other
+ * arguments may be queued back to back; four job tables are kept per upload, a fifth pair
+ * of arguments waits for the batch's work and reuses the oldest.  WVG_ERR_SPACE:
+ * cap_floats is less than wvg_batch_resample_floats; WVG_ERR_ARG: before an upload,
+ * out_rate < 1, out_rate > INT32_MAX, fixed_frames < 0.
+ *   wvg_batch_file_resample: file i's place in the image, *frames = min(F', L) (host only,
+ * as wvg_batch_file_planar).
+ *   Host only: wvg_resample_filter returns new * K and, with taps != NULL, fills the table
+ * row-major [new][K] (WVG_ERR_ARG: the pair is not supported; WVG_ERR_SPACE: cap_floats is
+ * short); wvg_resample_float runs the kernel's job builder and tile code (wv_resample.h)
+ * over one file's `frames` x `channels` interleaved ints: `channels` rows of row_stride
+ * floats at `out`, min(F', row_len) frames computed, +0.0f up to row_stride (>= row_len),
+ * kind = k (7 / 15 / 23 / 31; equal rates: wvg_planar_float); wvg_resample_tile_frames:
+ * the output frames of one job for a rate pair and a channel count (1..255). */
+int wvg_batch_resample(wvg_batch *b, int64_t out_rate, int64_t fixed_frames, float *dev_dst, int64_t cap_floats,
+                       void *stream);
+int64_t wvg_batch_resample_floats(const wvg_batch *b, int64_t out_rate, int64_t fixed_frames);
+int wvg_batch_file_resample(const wvg_batch *b, int file, int64_t out_rate, int64_t fixed_frames, int64_t *offset,
+                            int64_t *row_stride, int32_t *channels, int64_t *frames);
+float *wvg_batch_device_resampled(wvg_batch *b); /* the batch-owned image of the last dev_dst == NULL call */
+int wvg_batch_download_resampled(wvg_batch *b, float *host, int64_t cap_floats); /* that image; waits */
+int wvg_resample_filter(int64_t in_rate, int64_t out_rate, int32_t *orig, int32_t *new_, int32_t *width, float *taps,
+                        int64_t cap_floats);
+int wvg_resample_float(const int32_t *src, int64_t frames, int channels, int kind, int64_t in_rate, int64_t out_rate,
+                       int64_t row_len, int64_t row_stride, float *out);
+int wvg_resample_tile_frames(int64_t in_rate, int64_t out_rate, int channels);
+
 /* ---- Per-channel level statistics on the device (beyond the reference): what a consumer
  * of a decoded batch computes next -- peak, DC offset, RMS, clip count, where the audio
  * starts and ends -- as exact integers, 64 bytes per channel, with two kernels per batch

@@ -166,6 +166,16 @@ def lib():
         "wvg_batch_download_planar": (i32, [vp, vp, i64]),
         "wvg_planar_float": (i32, [vp, i64, i32, i32, i64, i64, vp]),
         "wvg_planar_tile_frames": (i32, [i32]),
+        "wvg_batch_resample": (i32, [vp, i64, i64, vp, i64, vp]),
+        "wvg_batch_resample_floats": (i64, [vp, i64, i64]),
+        "wvg_batch_file_resample": (i32, [vp, i32, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(i64)]),
+        "wvg_batch_device_resampled": (vp, [vp]),
+        "wvg_batch_download_resampled": (i32, [vp, vp, i64]),
+        "wvg_resample_filter": (i32, [i64, i64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                      ctypes.POINTER(ctypes.c_int32), vp, i64]),
+        "wvg_resample_float": (i32, [vp, i64, i32, i32, i64, i64, i64, i64, vp]),
+        "wvg_resample_tile_frames": (i32, [i64, i64, i32]),
         "wvg_batch_levels": (i32, [vp, u32, vp]),
         "wvg_batch_file_levels": (i32, [vp, i32, vp, i32]),
         "wvg_levels_ints": (i32, [vp, i64, i32, i32, u32, vp]),
@@ -198,6 +208,8 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_probe_file_streams", "wvg_batch_file_streams", "wvg_interleave_streams", "wvg_interleave_tile_frames",
             "wvg_batch_planar", "wvg_batch_planar_floats", "wvg_batch_file_planar", "wvg_batch_device_planar",
             "wvg_batch_download_planar", "wvg_planar_float", "wvg_planar_tile_frames",
+            "wvg_batch_resample", "wvg_batch_resample_floats", "wvg_batch_file_resample", "wvg_batch_device_resampled",
+            "wvg_batch_download_resampled", "wvg_resample_filter", "wvg_resample_float", "wvg_resample_tile_frames",
             "wvg_batch_levels", "wvg_batch_file_levels", "wvg_levels_ints", "wvg_levels_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of

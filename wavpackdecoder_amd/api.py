@@ -132,6 +132,7 @@ class DecodeBatch:
         self._dev_infos: list = []  # indices of device-framed files (their infos come with the upload)
         self._uploaded = False
         self._planar_fixed = 0  # fixed_frames of the last planar(out=None)
+        self._resample_key = (1, 0)  # (out_rate, fixed_frames) of the last resample(out=None)
         self._data: list = []
 
     def add_file(self, data: bytes, open_flags: int = 0, start_sample: int | None = None, wvc: bytes | None = None):
@@ -455,6 +456,71 @@ class DecodeBatch:
         self._check(self._L.wvg_batch_download_planar(self._b, out.ctypes.data, out.size))
         return out[:n]
 
+    def resample_floats(self, out_rate: int, fixed_frames: int = 0) -> int:
+        """Floats of the resampled image for (out_rate, fixed_frames) (wvg_batch_resample_floats)."""
+        n = int(self._L.wvg_batch_resample_floats(self._b, int(out_rate), int(fixed_frames)))
+        if n < 0:
+            raise ValueError("out_rate must be in 1..2^31-1 and fixed_frames >= 0")
+        return n
+
+    def file_resample(self, i: int, out_rate: int, fixed_frames: int = 0):
+        """(offset, row_stride, channels, frames) of file i in the resampled image
+        (wvg_batch_file_resample), frames at out_rate; offset -1 for a file that is not
+        resamplable (it did not open, it is DSD or an exact-float decode, it has no sample
+        rate, or its rate pair is not supported)."""
+        off, rs, fr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        ch = ctypes.c_int32()
+        rc = self._L.wvg_batch_file_resample(self._b, int(i), int(out_rate), int(fixed_frames), ctypes.byref(off),
+                                             ctypes.byref(rs), ctypes.byref(ch), ctypes.byref(fr))
+        if rc == _L.WVG_ERR_ARG and not (1 <= int(out_rate) < 2 ** 31 and int(fixed_frames) >= 0):
+            raise ValueError("out_rate must be in 1..2^31-1 and fixed_frames >= 0")
+        if rc < 0 and rc != _L.WVG_ERR_OPEN:
+            self._check(rc)
+        return int(off.value), int(rs.value), int(ch.value), int(fr.value)
+
+    def resample(self, out_rate: int, fixed_frames: int = 0, out=None, stream=None):
+        """The decoded batch as planar float32 in [-1, 1) at one sample rate on the device
+        (wvg_batch_resample; the filter, the layout and the conversion: include/wvgpu.h),
+        after decode(), on `stream`, without waiting -- sync() covers it.  The mirror of
+        planar(): fixed_frames 0 gives every file's rows at their own resampled length
+        (padded to a multiple of 4 floats), T > 0 rows of T frames at out_rate, cut or
+        zero-padded.  out: a contiguous float32 torch tensor on the batch's device with room
+        for resample_floats(out_rate, fixed_frames) floats, or None for a buffer the batch
+        owns (download_resampled, device_resampled_ptr).  Returns (offset, row_stride,
+        channels, frames) per file, offset -1 for a file that is not resamplable."""
+        if not (1 <= int(out_rate) < 2 ** 31) or int(fixed_frames) < 0:
+            raise ValueError("out_rate must be in 1..2^31-1 and fixed_frames >= 0")
+        if not self._uploaded:
+            self.upload()
+        ptr, cap = None, 0
+        if out is not None:
+            torch = _torch()  # (only a caller that passes a tensor needs it)
+            if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32 or \
+                    not out.is_contiguous():
+                raise ValueError("out: a contiguous float32 torch tensor on the GPU")
+            if out.device.index != context_device():
+                raise ValueError(f"out is on {out.device}, the batch decodes on device {context_device()}")
+            ptr, cap = ctypes.c_void_p(out.data_ptr()), out.numel()
+        rc = self._L.wvg_batch_resample(self._b, int(out_rate), int(fixed_frames), ptr, cap, stream)
+        if rc == _L.WVG_ERR_SPACE:
+            raise ValueError(f"out holds {cap} floats, the image needs {self.resample_floats(out_rate, fixed_frames)}")
+        self._check(rc)
+        if out is None:
+            self._resample_key = (int(out_rate), int(fixed_frames))
+        return [self.file_resample(i, out_rate, fixed_frames) for i in range(len(self.infos))]
+
+    def device_resampled_ptr(self) -> int:
+        """Device pointer of the batch-owned resampled image (the last resample(out=None))."""
+        return int(self._L.wvg_batch_device_resampled(self._b) or 0)
+
+    def download_resampled(self) -> np.ndarray:
+        """The batch-owned image of the last resample(out=None), as a flat float32 array
+        (wvg_batch_download_resampled; waits for it)."""
+        n = self.resample_floats(*self._resample_key)
+        out = np.empty(max(n, 1), dtype=np.float32)
+        self._check(self._L.wvg_batch_download_resampled(self._b, out.ctypes.data, out.size))
+        return out[:n]
+
     def levels(self, threshold_q31: int = 0, stream=None):
         """Every measurable file's per-channel level statistics on the device
         (wvg_batch_levels; the fields: include/wvgpu.h), after decode(), on `stream`, without
@@ -741,7 +807,56 @@ def planar_float(src: np.ndarray, kind: int, row_len: int | None = None, row_str
     return out[: nch * row_stride].reshape(nch, row_stride)
 
 
-def decode_to_tensors(files, open_flags: int = 0, fixed_frames: int = 0):
+def resample_filter(in_rate: int, out_rate: int):
+    """The resampler's filter for a rate pair (wvg_resample_filter): (orig, new, width,
+    float32 taps of shape [new, K]); ValueError for a pair that is not supported."""
+    L = _L.lib()
+    o, n, w = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    cnt = L.wvg_resample_filter(int(in_rate), int(out_rate), ctypes.byref(o), ctypes.byref(n), ctypes.byref(w), None, 0)
+    if cnt < 0:
+        raise ValueError(f"resample_filter: {in_rate} -> {out_rate} is not a supported pair")
+    taps = np.empty(cnt, dtype=np.float32)
+    cnt = L.wvg_resample_filter(int(in_rate), int(out_rate), None, None, None, taps.ctypes.data, taps.size)
+    if cnt < 0:
+        raise ValueError(f"wvg_resample_filter: {cnt}")
+    return int(o.value), int(n.value), int(w.value), taps.reshape(int(n.value), -1)
+
+
+def resample_tile_frames(in_rate: int, out_rate: int, channels: int) -> int:
+    """Output frames of one job of the resample kernel for a rate pair and a channel count
+    (wv_resample.h)."""
+    t = _L.lib().wvg_resample_tile_frames(int(in_rate), int(out_rate), int(channels))
+    if t < 0:
+        raise ValueError("channels must be in 1..255 and the rate pair supported")
+    return int(t)
+
+
+def resample_float(src: np.ndarray, kind: int, in_rate: int, out_rate: int, row_len: int | None = None,
+                   row_stride: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+    """The resample kernel's job builder and tile code run on the host (wvg_resample_float):
+    `src` is int32 of shape (frames, channels) at in_rate; kind 7 / 15 / 23 / 31 scales by
+    2^-kind.  Returns float32 of shape (channels, row_stride) at out_rate (row_len defaults
+    to the resampled length ceil(frames * new / orig), row_stride to row_len).  out: a flat
+    float32 array to write into."""
+    a = np.ascontiguousarray(src, dtype=np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    frames, nch = a.shape
+    if row_len is None:
+        g = math.gcd(int(in_rate), int(out_rate)) if in_rate > 0 and out_rate > 0 else 1
+        o, n = int(in_rate) // g, int(out_rate) // g
+        row_len = -(-frames * n // o) if o else 0
+    row_len = int(row_len)
+    row_stride = row_len if row_stride is None else int(row_stride)
+    if out is None:
+        out = np.empty(max(nch * row_stride, 1), dtype=np.float32)
+    rc = _L.lib().wvg_resample_float(a.ctypes.data, frames, nch, int(kind), int(in_rate), int(out_rate), row_len,
+                                     row_stride, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_resample_float: {rc}")
+    return out[: nch * row_stride].reshape(nch, row_stride)
+
+
+def decode_to_tensors(files, open_flags: int = 0, fixed_frames: int = 0, sample_rate: int = 0):
     """Decode `files` into float32 torch tensors on the GPU, channels first, in [-1, 1):
     add, upload, decode and planar() on torch's current stream of the batch's device, into
     one flat tensor, with nothing downloaded.  fixed_frames 0: a list with a [C_i, T_i]
@@ -749,26 +864,37 @@ def decode_to_tensors(files, open_flags: int = 0, fixed_frames: int = 0):
     fixed_frames T > 0: (tensor [B, C, T], lengths) over the convertible files in file
     order, every file cut or zero-padded to T frames, lengths[i] = its frames in the
     tensor; ValueError when their channel counts differ.  Work queued on the same torch
-    stream afterwards sees the tensors complete."""
+    stream afterwards sees the tensors complete.  sample_rate R > 0: every file is
+    resampled to R on the device (resample() in place of planar()); lengths and T count
+    frames at R, and a file that is not resamplable is None or left out."""
     torch = _torch()  # lazily: the package imports without it
-    fixed_frames = int(fixed_frames)
+    fixed_frames, sample_rate = int(fixed_frames), int(sample_rate)
     if fixed_frames < 0:
         raise ValueError("fixed_frames must be >= 0")
+    if sample_rate < 0 or sample_rate >= 2 ** 31:
+        raise ValueError("sample_rate must be in 0..2^31-1")
     b = DecodeBatch(SAMPLE_BUFFER_SIZE)
     try:
         dev = torch.device("cuda", context_device())
         if len(files):
             b.add_files(files, open_flags)
         b.upload()
-        lay = [b.file_planar(i, fixed_frames) for i in range(len(b.infos))]
+        if sample_rate:
+            lay = [b.file_resample(i, sample_rate, fixed_frames) for i in range(len(b.infos))]
+        else:
+            lay = [b.file_planar(i, fixed_frames) for i in range(len(b.infos))]
         conv = [l for l in lay if l[0] >= 0]
         if fixed_frames and len({l[2] for l in conv}) > 1:
             raise ValueError("fixed_frames needs files of one channel count, got " +
                              str(sorted({l[2] for l in conv})))
-        flat = torch.empty(b.planar_floats(fixed_frames), dtype=torch.float32, device=dev)
+        floats = b.resample_floats(sample_rate, fixed_frames) if sample_rate else b.planar_floats(fixed_frames)
+        flat = torch.empty(floats, dtype=torch.float32, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         b.decode(stream)
-        b.planar(fixed_frames, out=flat, stream=stream)
+        if sample_rate:
+            b.resample(sample_rate, fixed_frames, out=flat, stream=stream)
+        else:
+            b.planar(fixed_frames, out=flat, stream=stream)
         if fixed_frames:
             nch = conv[0][2] if conv else 0
             return flat.view(len(conv), nch, fixed_frames), [l[3] for l in conv]

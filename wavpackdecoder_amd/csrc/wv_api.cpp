@@ -8,7 +8,9 @@
 #include <atomic>
 #include <cstddef>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -22,6 +24,7 @@
 #include "wv_mc.h"
 #include "wv_md5.h"
 #include "wv_planar.h"
+#include "wv_resample.h"
 
 namespace wvg {
 hipError_t launch_decode(const BlockDesc *descs, const uint32_t *pcm_list, uint32_t n_pcm, const uint32_t *dsd_list,
@@ -40,6 +43,7 @@ hipError_t launch_md5(const Md5Job *jobs, uint32_t njobs, const int32_t *out, ui
 hipError_t launch_mc(const McJob *jobs, uint32_t njobs, const McStreamDev *streams, int32_t *out, int plain,
                      hipStream_t s);
 hipError_t launch_planar(const PlJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
+hipError_t launch_resample(const RsJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
 hipError_t launch_levels(const LvJob *jobs, uint32_t njobs, const LvFold *folds, uint32_t nfolds, const int32_t *in,
                          LvRecord *partials, LvRecord *out, uint32_t threshold_q31, hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
@@ -293,6 +297,35 @@ struct wvg_batch {
     mutable std::vector<int64_t> pl_off;
     mutable int64_t pl_lay_fixed = 0, pl_lay_floats = 0;
     mutable bool pl_lay_valid = false;
+    // wvg_batch_resample (wv_resample.h): planar's scheme with (out_rate, fixed_frames) as the
+    // key -- a job table is built and sent once per upload and key into a staging buffer
+    // and a device table of its own; with all kPlTables in use the batch's work is waited
+    // for and the oldest is reused (four kept, a fifth waits).  A filter table is built and
+    // sent once per (in_rate, out_rate) into an allocation of its own that lives as long as
+    // the batch: the jobs hold its address, and no later call rewrites it.
+    struct RsFilterDev {
+        int64_t in_rate = 0, out_rate = 0;
+        int32_t orig = 0, new_ = 0, width = 0, taps = 0;
+        PinnedBuf stage;
+        float *d_tab = nullptr;
+    };
+    std::vector<std::unique_ptr<RsFilterDev>> rs_filters;
+    struct RsTable {
+        int64_t rate = 0, fixed = 0, floats = 0;
+        bool valid = false;
+        PinnedBuf stage;
+        RsJob *d_jobs = nullptr;
+        size_t cap = 0;
+        uint32_t njobs = 0;
+    };
+    RsTable rs[kPlTables];
+    int rs_next = 0;
+    float *d_resampled = nullptr;  // the batch-owned image (dev_dst == NULL), not planar's
+    size_t cap_resampled = 0;
+    int64_t resampled_floats = -1;  // its floats after the last such call, -1 none since the upload
+    mutable std::vector<int64_t> rs_off;  // the layout for one (out_rate, fixed_frames): -1 not resamplable
+    mutable int64_t rs_lay_rate = 0, rs_lay_fixed = 0, rs_lay_floats = 0;
+    mutable bool rs_lay_valid = false;
     // wvg_batch_levels (wv_levels.h): one job per (measurable file, frame tile) and one fold
     // per (measurable file, channel), built and sent once per upload.  The threshold is a
     // kernel argument, so calls with other thresholds share the tables.  They share the
@@ -348,6 +381,61 @@ static void pl_file_jobs(uint64_t in_off, uint64_t out_off, uint64_t row_stride,
         j.kind = kind;
         emit(j);
     }
+}
+
+// the reduced rates and the size of a rate pair's filter (include/wvgpu.h)
+struct RsFilter {
+    int32_t orig = 0, new_ = 0, width = 0, taps = 0;
+};
+
+// wvg_batch_resample's jobs (wv_resample.h), the tiles of one file's rows: output frames
+// [0, row_stride), the file's own up to `valid` (<= F'); `frames`: F
+template <class E>
+static void rs_file_jobs(uint64_t in_off, uint64_t out_off, uint64_t row_stride, uint64_t valid, uint64_t frames,
+                         uint32_t nch, uint32_t kind, const RsFilter &f, const float *tab, E &&emit) {
+    const RsGeom g = rs_geom((uint32_t)f.orig, (uint32_t)f.new_, (uint32_t)f.taps, nch);
+    const uint64_t tf = (uint64_t)g.nb * (uint64_t)f.new_;
+    for (uint64_t f0 = 0; f0 < row_stride; f0 += tf) {
+        const uint64_t left = row_stride - f0, have = valid > f0 ? valid - f0 : 0;
+        for (uint32_t c0 = 0; c0 < nch; c0 += g.cg) {
+            RsJob j;
+            j.in_off = in_off;
+            j.out_off = out_off + (uint64_t)c0 * row_stride + f0;
+            j.row_stride = row_stride;
+            j.frames = frames;
+            j.win0 = (int64_t)(f0 / (uint64_t)f.new_) * (int64_t)f.orig - (int64_t)f.width;
+            j.tab = tab;
+            j.orig = (uint32_t)f.orig;
+            j.new_ = (uint32_t)f.new_;
+            j.taps = (uint32_t)f.taps;
+            j.nframes = (uint32_t)(left < tf ? left : tf);
+            j.nvalid = (uint32_t)(have < (uint64_t)j.nframes ? have : j.nframes);
+            j.nb = (j.nvalid + (uint32_t)f.new_ - 1u) / (uint32_t)f.new_;
+            j.nch = nch;
+            j.c0 = c0;
+            j.cg = nch - c0 < g.cg ? nch - c0 : g.cg;
+            j.kind = kind;
+            emit(j);
+        }
+    }
+}
+
+// a same-rate file's jobs: planar's
+template <class E>
+static void rs_same_jobs(uint64_t in_off, uint64_t out_off, uint64_t row_stride, uint64_t valid, uint32_t nch,
+                         uint32_t kind, E &&emit) {
+    pl_file_jobs(in_off, out_off, row_stride, valid, nch, kind, [&](const PlJob &p) {
+        RsJob j;
+        memset(&j, 0, sizeof j);
+        j.in_off = p.in_off;
+        j.out_off = p.out_off;
+        j.row_stride = p.row_stride;
+        j.nframes = p.nframes;
+        j.nvalid = p.nvalid;
+        j.nch = j.cg = p.nch;
+        j.kind = p.kind;
+        emit(j);
+    });
 }
 
 // the tiles of one file (wv_levels.h) and its folds; `part`: its first record in the partials
@@ -524,6 +612,19 @@ static void free_dev(wvg_batch *b) {
         t.cap = 0;
         t.valid = false;
     }
+    for (auto &t : b->rs) {
+        hipFree(t.d_jobs);
+        t.d_jobs = nullptr;
+        t.cap = 0;
+        t.valid = false;
+    }
+    for (auto &f : b->rs_filters) hipFree(f->d_tab);
+    b->rs_filters.clear();
+    hipFree(b->d_resampled);
+    b->d_resampled = nullptr;
+    b->cap_resampled = 0;
+    b->resampled_floats = -1;
+    b->rs_lay_valid = false;
     hipFree(b->d_planar);
     b->d_planar = nullptr;
     b->cap_planar = 0;
@@ -589,6 +690,11 @@ static void planar_forget(wvg_batch *b) {
     b->pl_next = 0;
     b->planar_floats = -1;
     b->pl_lay_valid = false;
+    // (and wvg_batch_resample's; its filter tables do not depend on the upload and stay)
+    for (auto &t : b->rs) t.valid = false;
+    b->rs_next = 0;
+    b->resampled_floats = -1;
+    b->rs_lay_valid = false;
 }
 
 // Grow the page-locked blob: a larger one is a new allocation, so a DMA still
@@ -2355,6 +2461,290 @@ int wvg_planar_float(const int32_t *src, int64_t frames, int channels, int kind,
                      for (uint32_t tid = 0; tid < kPlThreads; tid++)
                          pl_load(j, src + j.in_off, out + j.out_off, t, tid, kPlThreads);
                      for (uint32_t tid = 0; tid < kPlThreads; tid++) pl_store(j, t, out + j.out_off, tid, kPlThreads);
+                 });
+    return WVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Planar float32 at one sample rate on the device (wv_resample.hip)
+// ---------------------------------------------------------------------------
+// the reduced rates and the filter's size; false: the pair is not supported (include/wvgpu.h)
+static bool rs_pair(int64_t in_rate, int64_t out_rate, RsFilter &f) {
+    if (in_rate < 1 || out_rate < 1) return false;
+    int64_t a = in_rate, g = out_rate;
+    while (a) {
+        const int64_t t = g % a;
+        g = a;
+        a = t;
+    }
+    const int64_t orig = in_rate / g, new_ = out_rate / g;
+    if (orig > (int64_t)kRsMaxRatio || new_ > (int64_t)kRsMaxRatio) return false;
+    const double base = (double)(orig < new_ ? orig : new_) * 0.99;
+    const double width = ceil(6.0 * (double)orig / base);
+    const double taps = 2.0 * width + (double)orig;
+    if (taps > (double)kRsMaxTaps) return false;
+    f.orig = (int32_t)orig;
+    f.new_ = (int32_t)new_;
+    f.width = (int32_t)width;
+    f.taps = (int32_t)taps;
+    return true;
+}
+
+// tap j of phase p: the Hann-windowed sinc in float64, flushed below 2^-64, rounded once
+static float rs_tap(const RsFilter &f, int p, int j) {
+    const double lpw = 6.0, pi = 3.14159265358979323846;
+    const double base = (double)(f.orig < f.new_ ? f.orig : f.new_) * 0.99;
+    double t = (-(double)p / (double)f.new_ + (double)(j - f.width) / (double)f.orig) * base;
+    t = t < -lpw ? -lpw : t > lpw ? lpw : t;
+    const double w = cos(t * pi / lpw / 2.0), tp = t * pi;
+    const double h = (tp == 0.0 ? 1.0 : sin(tp) / tp) * w * w * (base / (double)f.orig);
+    return fabs(h) < 0x1p-64 ? 0.0f : (float)h;
+}
+
+// the kernel's table: tab[j * npad + p], npad = (new + 1) & ~1, the pad +0.0f
+static void rs_table(const RsFilter &f, float *tab) {
+    const size_t npad = ((size_t)f.new_ + 1u) & ~(size_t)1;
+    for (int j = 0; j < f.taps; j++) {
+        for (int p = 0; p < f.new_; p++) tab[(size_t)j * npad + (size_t)p] = rs_tap(f, p, j);
+        if (npad > (size_t)f.new_) tab[(size_t)j * npad + (size_t)f.new_] = 0.0f;
+    }
+}
+
+static size_t rs_table_floats(const RsFilter &f) { return (size_t)f.taps * (((size_t)f.new_ + 1u) & ~(size_t)1); }
+
+// F': the output frames of F input frames
+static int64_t rs_out_frames(int64_t frames, const RsFilter &f) {
+    return (int64_t)(((uint64_t)frames * (uint64_t)f.new_ + (uint64_t)f.orig - 1u) / (uint64_t)f.orig);
+}
+
+// 0 not resamplable, 1 by the filter `f`, 2 at the caller's rate already (no filter)
+static int rs_resamplable(const wvg_batch *b, size_t i, int64_t out_rate, RsFilter &f) {
+    const FileInfo &fi = b->finfo[i];
+    if (!pl_convertible(b, i) || (fi.is_float && fi.exact_float)) return 0;
+    const int64_t in_rate = b->infos[i].sample_rate;
+    if (in_rate <= 0) return 0;
+    if (in_rate == out_rate) return 2;
+    return rs_pair(in_rate, out_rate, f) ? 1 : 0;
+}
+
+// a file's output frames F' and its row stride
+static int64_t rs_file_frames(const FileInfo &fi, int how, const RsFilter &f) {
+    return how == 2 ? fi.out_frames : rs_out_frames(fi.out_frames, f);
+}
+
+static int64_t rs_row_stride(int64_t oframes, int64_t fixed) {
+    return fixed > 0 ? fixed : (oframes + 3) & ~(int64_t)3;
+}
+
+static bool rs_args_ok(int64_t out_rate, int64_t fixed) {
+    return out_rate >= 1 && out_rate <= 0x7fffffffLL && fixed >= 0;
+}
+
+// the image layout for (out_rate, fixed) (include/wvgpu.h): kept while the batch stays uploaded
+static void rs_layout(const wvg_batch *b, int64_t out_rate, int64_t fixed) {
+    if (b->rs_lay_valid && b->rs_lay_rate == out_rate && b->rs_lay_fixed == fixed &&
+        b->rs_off.size() == b->finfo.size())
+        return;
+    b->rs_off.assign(b->finfo.size(), -1);
+    int64_t off = 0;
+    for (size_t i = 0; i < b->finfo.size(); i++) {
+        RsFilter f;
+        const int how = rs_resamplable(b, i, out_rate, f);
+        if (!how) continue;
+        b->rs_off[i] = off;
+        off += (int64_t)b->finfo[i].out_nch * rs_row_stride(rs_file_frames(b->finfo[i], how, f), fixed);
+    }
+    b->rs_lay_floats = off;
+    b->rs_lay_rate = out_rate;
+    b->rs_lay_fixed = fixed;
+    b->rs_lay_valid = b->uploaded;
+}
+
+int64_t wvg_batch_resample_floats(const wvg_batch *b, int64_t out_rate, int64_t fixed_frames) {
+    if (!b || !rs_args_ok(out_rate, fixed_frames)) return WVG_ERR_ARG;
+    rs_layout(b, out_rate, fixed_frames);
+    return b->rs_lay_floats;
+}
+
+int wvg_batch_file_resample(const wvg_batch *b, int file, int64_t out_rate, int64_t fixed_frames, int64_t *offset,
+                            int64_t *row_stride, int32_t *channels, int64_t *frames) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || !rs_args_ok(out_rate, fixed_frames)) return WVG_ERR_ARG;
+    rs_layout(b, out_rate, fixed_frames);
+    const FileInfo &fi = b->finfo[(size_t)file];
+    const bool ok = b->rs_off[(size_t)file] >= 0;
+    RsFilter f;
+    const int how = ok ? rs_resamplable(b, (size_t)file, out_rate, f) : 0;
+    const int64_t of = ok ? rs_file_frames(fi, how, f) : 0;
+    if (offset) *offset = b->rs_off[(size_t)file];
+    if (row_stride) *row_stride = ok ? rs_row_stride(of, fixed_frames) : 0;
+    if (channels) *channels = ok ? fi.out_nch : 0;
+    if (frames) *frames = fixed_frames > 0 && fixed_frames < of ? fixed_frames : of;
+    return ok ? WVG_OK : WVG_ERR_OPEN;
+}
+
+// the batch's device table of a rate pair, built and sent on first use
+static int rs_filter_dev(wvg_batch *b, int64_t in_rate, int64_t out_rate, const RsFilter &f, const float **tab) {
+    for (auto &x : b->rs_filters)
+        if (x->in_rate == in_rate && x->out_rate == out_rate) {
+            *tab = x->d_tab;
+            return WVG_OK;
+        }
+    wvg_ctx *c = b->ctx;
+    std::unique_ptr<wvg_batch::RsFilterDev> x(new wvg_batch::RsFilterDev);
+    const size_t nb = sizeof(float) * rs_table_floats(f);
+    if (!x->stage.resize(nb)) return WVG_ERR_SPACE;
+    rs_table(f, reinterpret_cast<float *>(x->stage.data()));
+    HIPCHK(c, hipMalloc((void **)&x->d_tab, nb));
+    x->in_rate = in_rate;
+    x->out_rate = out_rate;
+    x->orig = f.orig;
+    x->new_ = f.new_;
+    x->width = f.width;
+    x->taps = f.taps;
+    *tab = x->d_tab;
+    b->rs_filters.push_back(std::move(x));  // (owned from here on: a failed copy leaves it to the batch's free)
+    HIPCHK(c, hipMemcpyAsync(b->rs_filters.back()->d_tab, b->rs_filters.back()->stage.data(), nb,
+                             hipMemcpyHostToDevice, b->stream));
+    HIPCHK(c, hipEventRecord(b->up, b->stream));
+    return WVG_OK;
+}
+
+int wvg_batch_resample(wvg_batch *b, int64_t out_rate, int64_t fixed_frames, float *dev_dst, int64_t cap_floats,
+                       void *stream) {
+    if (!b || !b->uploaded || !rs_args_ok(out_rate, fixed_frames)) return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    rs_layout(b, out_rate, fixed_frames);
+    const int64_t floats = b->rs_lay_floats;
+    if (dev_dst && cap_floats < floats) return WVG_ERR_SPACE;
+    wvg_batch::RsTable *t = nullptr;
+    for (auto &x : b->rs)
+        if (x.valid && x.rate == out_rate && x.fixed == fixed_frames) t = &x;
+    if (!t) {
+        t = &b->rs[b->rs_next];
+        // a table in use by this upload's earlier calls: they must have finished with it
+        if (t->valid) HIPCHK(c, quiesce(b));
+        t->valid = false;
+        b->rs_next = (b->rs_next + 1) % kPlTables;
+        std::vector<RsJob> jobs;
+        for (size_t i = 0; i < b->finfo.size(); i++) {
+            if (b->rs_off[i] < 0) continue;
+            const FileInfo &fi = b->finfo[i];
+            RsFilter f;
+            const int how = rs_resamplable(b, i, out_rate, f);
+            const int64_t of = rs_file_frames(fi, how, f);
+            const uint64_t rs = (uint64_t)rs_row_stride(of, fixed_frames);
+            const uint64_t valid = (uint64_t)(of < (int64_t)rs ? of : (int64_t)rs);
+            auto emit = [&](const RsJob &j) { jobs.push_back(j); };
+            if (how == 2) {
+                rs_same_jobs((uint64_t)b->infos[i].out_offset, (uint64_t)b->rs_off[i], rs, valid, (uint32_t)fi.out_nch,
+                             pl_kind(b, i), emit);
+            } else {
+                const float *tab = nullptr;
+                const int rc = rs_filter_dev(b, b->infos[i].sample_rate, out_rate, f, &tab);
+                if (rc != WVG_OK) return rc;
+                rs_file_jobs((uint64_t)b->infos[i].out_offset, (uint64_t)b->rs_off[i], rs, valid,
+                             (uint64_t)fi.out_frames, (uint32_t)fi.out_nch, pl_kind(b, i), f, tab, emit);
+            }
+            if (jobs.size() > 0x7fffffffu) return WVG_ERR_SPACE;
+        }
+        const size_t jb = sizeof(RsJob) * (jobs.empty() ? 1 : jobs.size());
+        if (!t->stage.resize(jb)) return WVG_ERR_SPACE;
+        HIPCHK(c, ensure(t->d_jobs, t->cap, jb));
+        if (!jobs.empty()) {
+            memcpy(t->stage.data(), jobs.data(), sizeof(RsJob) * jobs.size());
+            // on the batch stream, behind the upload's copies; `up` is recorded again so that a
+            // call on a caller's stream waits for the table too (as wvg_batch_planar's)
+            HIPCHK(c, hipMemcpyAsync(t->d_jobs, t->stage.data(), sizeof(RsJob) * jobs.size(), hipMemcpyHostToDevice,
+                                     b->stream));
+            HIPCHK(c, hipEventRecord(b->up, b->stream));
+        }
+        t->njobs = (uint32_t)jobs.size();
+        t->rate = out_rate;
+        t->fixed = fixed_frames;
+        t->floats = floats;
+        t->valid = true;
+    }
+    float *dst = dev_dst;
+    if (!dst) {
+        const size_t nb = sizeof(float) * (size_t)(floats ? floats : 1);
+        // (growing frees the old image: an earlier call may still be writing it)
+        if (nb > b->cap_resampled && b->d_resampled) HIPCHK(c, quiesce(b));
+        HIPCHK(c, ensure(b->d_resampled, b->cap_resampled, nb));
+        dst = b->d_resampled;
+        b->resampled_floats = floats;
+    }
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_resample(t->d_jobs, t->njobs, b->d_out, dst, s));
+    HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
+    return WVG_OK;
+}
+
+float *wvg_batch_device_resampled(wvg_batch *b) { return b && b->resampled_floats >= 0 ? b->d_resampled : nullptr; }
+
+int wvg_batch_download_resampled(wvg_batch *b, float *host, int64_t cap_floats) {
+    if (!b || b->resampled_floats < 0 || (!host && b->resampled_floats)) return WVG_ERR_ARG;
+    if (cap_floats < b->resampled_floats) return WVG_ERR_SPACE;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamWaitEvent(b->stream, b->done, 0));
+    if (b->resampled_floats)
+        HIPCHK(c, hipMemcpyAsync(host, b->d_resampled, sizeof(float) * (size_t)b->resampled_floats,
+                                 hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(c, hipStreamSynchronize(b->stream));
+    return WVG_OK;
+}
+
+int wvg_resample_filter(int64_t in_rate, int64_t out_rate, int32_t *orig, int32_t *new_, int32_t *width, float *taps,
+                        int64_t cap_floats) {
+    RsFilter f;
+    if (!rs_pair(in_rate, out_rate, f)) return WVG_ERR_ARG;
+    if (orig) *orig = f.orig;
+    if (new_) *new_ = f.new_;
+    if (width) *width = f.width;
+    const int64_t n = (int64_t)f.new_ * f.taps;
+    if (taps) {
+        if (cap_floats < n) return WVG_ERR_SPACE;
+        for (int p = 0; p < f.new_; p++)
+            for (int j = 0; j < f.taps; j++) taps[(size_t)p * (size_t)f.taps + (size_t)j] = rs_tap(f, p, j);
+    }
+    return (int)n;
+}
+
+int wvg_resample_tile_frames(int64_t in_rate, int64_t out_rate, int channels) {
+    if (channels < 1 || channels > (int)kPlMaxChannels || in_rate < 1 || out_rate < 1) return WVG_ERR_ARG;
+    if (in_rate == out_rate) return (int)pl_tile_frames((uint32_t)channels);
+    RsFilter f;
+    if (!rs_pair(in_rate, out_rate, f)) return WVG_ERR_ARG;
+    return (int)(rs_geom((uint32_t)f.orig, (uint32_t)f.new_, (uint32_t)f.taps, (uint32_t)channels).nb * (uint32_t)f.new_);
+}
+
+int wvg_resample_float(const int32_t *src, int64_t frames, int channels, int kind, int64_t in_rate, int64_t out_rate,
+                       int64_t row_len, int64_t row_stride, float *out) {
+    if (in_rate >= 1 && in_rate == out_rate) return wvg_planar_float(src, frames, channels, kind, row_len, row_stride, out);
+    RsFilter f;
+    if (channels < 1 || channels > (int)kPlMaxChannels || frames < 0 || row_len < 0 || row_stride < row_len ||
+        (kind != 7 && kind != 15 && kind != 23 && kind != 31) || (frames && row_len && !src) || (row_stride && !out) ||
+        !rs_pair(in_rate, out_rate, f))
+        return WVG_ERR_ARG;
+    std::vector<float> tab(rs_table_floats(f));
+    rs_table(f, tab.data());
+    const int64_t of = rs_out_frames(frames, f);
+    // the kernel's tile code (wv_resample.h), the workgroup's threads as a loop
+    std::vector<uint32_t> lds(kRsLdsFloats + 4, 0u);
+    uint32_t *xw = lds.data();
+    while ((uintptr_t)xw & 15u) xw++;
+    uint32_t *yt = xw + kRsXFloats;
+    rs_file_jobs(0, 0, (uint64_t)row_stride, (uint64_t)(of < row_len ? of : row_len), (uint64_t)frames,
+                 (uint32_t)channels, (uint32_t)kind, f, tab.data(), [&](const RsJob &j) {
+                     float *dst = out + j.out_off;
+                     if (j.nvalid) {
+                         for (uint32_t tid = 0; tid < kRsThreads; tid++) rs_load(j, src + j.in_off, xw, tid, kRsThreads);
+                         for (uint32_t tid = 0; tid < kRsThreads; tid++) rs_fir(j, xw, yt, dst, tid, kRsThreads);
+                     }
+                     for (uint32_t tid = 0; tid < kRsThreads; tid++) rs_store(j, yt, dst, tid, kRsThreads);
                  });
     return WVG_OK;
 }
