@@ -179,6 +179,58 @@ int wvg_interleave_streams(const int32_t *const *streams, const int32_t *widths,
                            int32_t *out);
 int wvg_interleave_tile_frames(int channels);
 
+/* ---- DSD files as 24-bit PCM (open_flags bit beyond the reference, whose DSD output is
+ * one byte value -- eight one-bit samples -- per channel-sample; WavPack's own library has
+ * OPEN_DSD_AS_PCM).  A DSD file added or probed with this flag presents itself as a 24-bit
+ * PCM file at the DSD byte rate: info.bits_per_sample = 24, bytes_per_sample = 3,
+ * sample_rate = the unflagged value / 8 (dsd_multiplier x the stored rate; 352,800 for
+ * DSD64), every other field as without the flag -- dsd_multiplier, mode, out_frames,
+ * total_samples, reduced_channels.  Its output is info.out_frames frames of
+ * info.reduced_channels interleaved int32 at info.out_offset, each within +-(2^23 - 1), and
+ * every later call works on it as on any 24-bit file: wvg_batch_format (3-byte little
+ * endian), md5, planar (k = 23), levels (k = 23), resample (352,800 -> 44,100 is 8:1, ->
+ * 48,000 is 147:20, -> 16,000 is 441:20: all inside the resampler's limits), and
+ * decode_to_tensors.  OPEN_2CH_MAX combines with it as it does without.  On a file that is
+ * not DSD the flag changes nothing: info, offsets, wvg_batch_out_ints, output.
+ *   The filter (fixed; exact integer arithmetic): T = 104 taps over bits, 13 bytes of history
+ * centred on the output's byte.  Tap t = 8 j + i is bit i of window byte j (j = 0 oldest;
+ * i = 0 the byte's MSB, the earliest in time).  In float64
+ *     x_t = clamp((t - 51.5) * 0.99 / 8, -6, +6)
+ *     h_t = sinc(pi x_t) * cos(pi x_t / 12)^2              (sinc(0) = 1)
+ *     c_t = trunc(h_t / sum |h| * (2^23 - 1))              (toward zero)
+ * -- wvg_batch_resample's Hann-windowed sinc (lpw 6, rolloff 0.99) at ratio 8:1, byte
+ * aligned.  The table is 104 committed integer constants (wvg_dsd_pcm_taps), symmetric, taps
+ * 0..3 and 100..103 zero, sum |c| = 8,388,570 <= 2^23 - 1 (no output can leave 24 bits: no
+ * clipping rule, no int32 overflow), sum c = 5,355,358: the DC gain is sum c / 2^23 = 0.638.
+ *   Output, with F = out_frames, C = ints per frame and src the decoded DSD ints:
+ *     B[q][c] = src[q * C + c] & 0xFF  for 0 <= q < F, else 0x55 (DSD's idle pattern)
+ *     s_i(b)  = +1 if (b >> (7 - i)) & 1 else -1
+ *     y[m][c] = sum_{j=0..12} sum_{i=0..7} c_{8j+i} * s_i(B[m - 6 + j][c])
+ * The filter runs over whatever the DSD decode left over out_frames, as format, md5 and
+ * planar define their input: a zero-filled gap or the frames after an exception are bytes
+ * of 0x00 (eight -1 bits).
+ *   Cost: the file's blocks decode into a staging range inside its part of the batch's int32
+ * output (16-byte aligned, before the visible range; only info.out_offset is contract), and
+ * one more kernel (wv_dsdpcm.hip) filters it into the visible range at the end of every
+ * wvg_batch_decode; wvg_batch_out_ints and a full wvg_batch_download include the staging
+ * (twice the file's output).  Statuses, wvg_file_result, wvg_batch_file_blocks and the
+ * kernel routing are those of the unflagged file.  wvg_batch_md5: the stored sum is over the
+ * DSD bytes, so the verdict is WVG_MD5_NOT_COMPARABLE; `computed` covers the 3-byte form.
+ *   Out of scope: WVG_ERR_ARG together with WVG_OPEN_ALL_CHANNELS (multichannel DSD; the
+ * kernel and wvg_dsd_pcm_ints take 1..255 channels, so that is a change to the framing's
+ * offsets only), with wvg_batch_add_file_at and wvg_batch_add_file_wvc; wvg_stream_open
+ * returns NULL; wvg_batch_add_files_device takes no flags; wvg_batch_wav returns WVG_ERR_ARG
+ * for a flagged DSD file (its stored header describes one-bit audio).  Other filters, a
+ * gain, and decimation past the byte rate are the resampler's job.
+ *   Host only: wvg_dsd_pcm_taps copies the table (*sum = sum c, *sum_abs = sum |c|; either may
+ * be NULL); wvg_dsd_pcm_ints runs the kernel's tile code (wv_dsdpcm.h) over `frames` x
+ * `channels` interleaved ints (channels 1..255, any 4-byte alignment, src != out);
+ * wvg_dsd_pcm_tile_frames: the frames of one tile for a channel count (1..255). */
+#define WVG_OPEN_DSD_AS_PCM 0x10000000u
+int wvg_dsd_pcm_taps(int32_t taps[104], int64_t *sum, int64_t *sum_abs);
+int wvg_dsd_pcm_ints(const int32_t *src, int64_t frames, int channels, int32_t *out);
+int wvg_dsd_pcm_tile_frames(int channels);
+
 /* A hybrid .wv file with its .wvc correction file: the hybrid blocks decode
  * EXACTLY (lossless) instead of the reference's lossy output.  Beyond the
  * reference (it opens ID_WVC_BITSTREAM, UnpackUtils.cs:96-106, but never reads
@@ -347,7 +399,8 @@ int wvg_batch_download_pcm_async(wvg_batch *b);
  * verdict, from framing facts only: NONE without a stored sum; NOT_COMPARABLE when a sum
  * is stored but this decode cannot reproduce the source bytes (a hybrid file without its
  * .wvc, lossy INT32 / float blocks, a float file without WVG_OPEN_EXACT_FLOAT, a file
- * added with wvg_batch_add_file_at or reduced by OPEN_2CH_MAX); else MATCH / MISMATCH
+ * added with wvg_batch_add_file_at or reduced by OPEN_2CH_MAX, a DSD file opened with
+ * WVG_OPEN_DSD_AS_PCM); else MATCH / MISMATCH
  * (a CRC error, a mute or an exception changes the output: MISMATCH).  `computed` is
  * always filled; `bytes` is the hashed length. */
 #define WVG_MD5_NONE 0
@@ -374,8 +427,9 @@ int wvg_md5_bytes(const uint8_t *data, size_t len, uint8_t digest[16]);
 /* ---- Planar float32 on the device (beyond the reference, which has no float output):
  * the decoded batch as float32 in [-1, 1), channels first, for a model, a resampler or
  * any DSP on the same device -- one kernel per batch (wv_planar.hip), no download.
- *   A file is convertible when it opened and is not DSD (a DSD byte holds eight one-bit
- * samples; decimation is out of scope).  The image holds the convertible files in file
+ *   A file is convertible when it opened and its output is not DSD bytes (a DSD byte holds
+ * eight one-bit samples; a DSD file opened with WVG_OPEN_DSD_AS_PCM is 24-bit PCM and
+ * convertible).  The image holds the convertible files in file
  * order, file i as C = info.reduced_channels rows (planes) of row_stride floats, row c at
  * float offset + c * row_stride; with F = info.out_frames:
  *     fixed_frames == 0 (ragged): row length L = F, row_stride = (F + 3) & ~3, offset =
@@ -450,7 +504,8 @@ int wvg_planar_tile_frames(int channels);
  * with j = 0 .. K-1 ascending: one accumulator, one order, fused multiply-adds.  A tap
  * outside the file adds exactly nothing.  in_rate == out_rate: no filter; the row is
  * planar's conversion bit for bit.
- *   A file is resamplable when it opened, is not DSD, is not a float file decoded under
+ *   A file is resamplable when it opened, its output is not DSD bytes (WVG_OPEN_DSD_AS_PCM
+ * makes a DSD file resamplable), is not a float file decoded under
  * WVG_OPEN_EXACT_FLOAT (levels' rule: use the default clipped 24-bit decode), has
  * sample_rate > 0, and its pair is supported.  The others take no room in the image: their
  * offset is -1 and wvg_batch_file_resample returns WVG_ERR_OPEN.  WVG_OPEN_ALL_CHANNELS
@@ -496,8 +551,8 @@ int wvg_resample_tile_frames(int64_t in_rate, int64_t out_rate, int channels);
  * of a decoded batch computes next -- peak, DC offset, RMS, clip count, where the audio
  * starts and ends -- as exact integers, 64 bytes per channel, with two kernels per batch
  * (wv_levels.hip) and no PCM downloaded: the statistics twin of wvg_batch_md5.
- *   A file is measurable when it opened, is not DSD (a DSD byte holds eight one-bit
- * samples) and is not a float file decoded under WVG_OPEN_EXACT_FLOAT (its ints are
+ *   A file is measurable when it opened, its output is not DSD bytes (a DSD byte holds eight
+ * one-bit samples; with WVG_OPEN_DSD_AS_PCM a DSD file is measured at k = 23) and is not a float file decoded under WVG_OPEN_EXACT_FLOAT (its ints are
  * IEEE-754 patterns, and sums of floats are not exact).  Measured is whatever the int32
  * output holds over info.out_frames frames of C = info.reduced_channels interleaved ints at
  * info.out_offset, as wvg_batch_format, md5 and planar: a file stopped by an exception has

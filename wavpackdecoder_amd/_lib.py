@@ -180,6 +180,9 @@ def lib():
         "wvg_batch_file_levels": (i32, [vp, i32, vp, i32]),
         "wvg_levels_ints": (i32, [vp, i64, i32, i32, u32, vp]),
         "wvg_levels_tile_frames": (i32, [i32]),
+        "wvg_dsd_pcm_taps": (i32, [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
+        "wvg_dsd_pcm_ints": (i32, [vp, i64, i32, vp]),
+        "wvg_dsd_pcm_tile_frames": (i32, [i32]),
     }
     for name, (res, args) in sig.items():
         try:
@@ -211,6 +214,7 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_batch_resample", "wvg_batch_resample_floats", "wvg_batch_file_resample", "wvg_batch_device_resampled",
             "wvg_batch_download_resampled", "wvg_resample_filter", "wvg_resample_float", "wvg_resample_tile_frames",
             "wvg_batch_levels", "wvg_batch_file_levels", "wvg_levels_ints", "wvg_levels_tile_frames",
+            "wvg_dsd_pcm_taps", "wvg_dsd_pcm_ints", "wvg_dsd_pcm_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of
 # letters and underscores only, so it cannot see a name with a digit in the header and

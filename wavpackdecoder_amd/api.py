@@ -57,6 +57,10 @@ OPEN_EXACT_FLOAT = 0x40000000
 # beyond the reference: a file of more than two channels opens and every channel is decoded
 # (WVG_OPEN_ALL_CHANNELS, include/wvgpu.h); not with OPEN_2CH_MAX, start_sample or wvc
 OPEN_ALL_CHANNELS = 0x20000000
+# beyond the reference: a DSD file opens as 24-bit PCM at the DSD byte rate, decimated on the
+# device (WVG_OPEN_DSD_AS_PCM, include/wvgpu.h); not with OPEN_ALL_CHANNELS, start_sample or
+# wvc; a file that is not DSD is unchanged
+OPEN_DSD_AS_PCM = 0x10000000
 
 
 class WavpackException(RuntimeError):
@@ -405,7 +409,7 @@ class DecodeBatch:
     def file_planar(self, i: int, fixed_frames: int = 0):
         """(offset, row_stride, channels, frames) of file i in the planar image
         (wvg_batch_file_planar); offset -1 for a file that is not convertible (it did not
-        open, or it is DSD)."""
+        open, or it is DSD opened without OPEN_DSD_AS_PCM)."""
         off, rs, fr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         ch = ctypes.c_int32()
         rc = self._L.wvg_batch_file_planar(self._b, int(i), int(fixed_frames), ctypes.byref(off), ctypes.byref(rs),
@@ -466,7 +470,7 @@ class DecodeBatch:
     def file_resample(self, i: int, out_rate: int, fixed_frames: int = 0):
         """(offset, row_stride, channels, frames) of file i in the resampled image
         (wvg_batch_file_resample), frames at out_rate; offset -1 for a file that is not
-        resamplable (it did not open, it is DSD or an exact-float decode, it has no sample
+        resamplable (it did not open, it is DSD opened without OPEN_DSD_AS_PCM or an exact-float decode, it has no sample
         rate, or its rate pair is not supported)."""
         off, rs, fr = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         ch = ctypes.c_int32()
@@ -536,7 +540,7 @@ class DecodeBatch:
     def file_levels(self, i: int):
         """File i's records of the last levels() (wvg_batch_file_levels; after sync()): a
         structured array (_lib.LEVELS_DTYPE) of one record per channel, or None for a file
-        that is not measurable (it did not open, it is DSD, or it is a float file decoded
+        that is not measurable (it did not open, it is DSD opened without OPEN_DSD_AS_PCM, or it is a float file decoded
         under OPEN_EXACT_FLOAT)."""
         n = self._L.wvg_batch_file_levels(self._b, int(i), None, 0)
         if n == _L.WVG_ERR_OPEN:
@@ -860,7 +864,8 @@ def decode_to_tensors(files, open_flags: int = 0, fixed_frames: int = 0, sample_
     """Decode `files` into float32 torch tensors on the GPU, channels first, in [-1, 1):
     add, upload, decode and planar() on torch's current stream of the batch's device, into
     one flat tensor, with nothing downloaded.  fixed_frames 0: a list with a [C_i, T_i]
-    view per file, None for a file that is not convertible (it did not open, or it is DSD).
+    view per file, None for a file that is not convertible (it did not open, or it is DSD
+    opened without OPEN_DSD_AS_PCM).
     fixed_frames T > 0: (tensor [B, C, T], lengths) over the convertible files in file
     order, every file cut or zero-padded to T frames, lengths[i] = its frames in the
     tensor; ValueError when their channel counts differ.  Work queued on the same torch
@@ -919,6 +924,48 @@ def verify_files(files, open_flags: int = 0) -> list:
         return [b.file_md5(i) if i >= 0 else None for i in idx]
     finally:
         b.close()
+
+
+def dsd_pcm_taps():
+    """The decimation filter of OPEN_DSD_AS_PCM (wvg_dsd_pcm_taps): (taps, sum, sum_abs) -- 104
+    int32 taps over bits, oldest first, and their sums as Python ints.  The DC gain is
+    sum / 2^23."""
+    taps = np.zeros(104, dtype=np.int32)
+    s, a = ctypes.c_int64(), ctypes.c_int64()
+    rc = _L.lib().wvg_dsd_pcm_taps(taps.ctypes.data, ctypes.byref(s), ctypes.byref(a))
+    if rc != 0:
+        raise ValueError(f"wvg_dsd_pcm_taps: {rc}")
+    return taps, int(s.value), int(a.value)
+
+
+def dsd_pcm_tile_frames(channels: int) -> int:
+    """Frames of one tile of the DSD-to-PCM kernel for a channel count (wv_dsdpcm.h)."""
+    t = _L.lib().wvg_dsd_pcm_tile_frames(int(channels))
+    if t < 0:
+        raise ValueError("channels must be in 1..255")
+    return int(t)
+
+
+def dsd_pcm_ints(src: np.ndarray, out: np.ndarray | None = None) -> np.ndarray:
+    """The DSD-to-PCM kernel's tile code run on the host (wvg_dsd_pcm_ints): `src` is int32 of
+    shape (frames, channels) -- decoded DSD, one byte value per int, only the low 8 bits
+    count; any int alignment -- and the result is int32 of the same shape, 24-bit PCM at the
+    byte rate.  `out`: a C-contiguous int32 destination of that shape (not `src`)."""
+    a = np.asarray(src)
+    if a.dtype != np.int32:
+        a = a.astype(np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    if not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    frames, nch = a.shape
+    if out is None:
+        out = np.zeros((frames, nch), dtype=np.int32)
+    elif out.dtype != np.int32 or out.shape != (frames, nch) or not out.flags.c_contiguous:
+        raise ValueError("out must be C-contiguous int32 of src's shape")
+    rc = _L.lib().wvg_dsd_pcm_ints(a.ctypes.data, frames, nch, out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_dsd_pcm_ints: {rc}")
+    return out
 
 
 def levels_tile_frames(channels: int) -> int:

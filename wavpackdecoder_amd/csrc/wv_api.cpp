@@ -18,6 +18,7 @@
 
 #include "../../include/wvgpu.h"
 #include "wv_desc.h"
+#include "wv_dsdpcm.h"
 #include "wv_format.h"
 #include "wv_framing.h"
 #include "wv_levels.h"
@@ -42,6 +43,7 @@ hipError_t launch_format(const FormatSeg *segs, uint32_t nseg, const int32_t *in
 hipError_t launch_md5(const Md5Job *jobs, uint32_t njobs, const int32_t *out, uint8_t *digests, hipStream_t s);
 hipError_t launch_mc(const McJob *jobs, uint32_t njobs, const McStreamDev *streams, int32_t *out, int plain,
                      hipStream_t s);
+hipError_t launch_dsdpcm(const DpJob *jobs, uint32_t njobs, int32_t *out, hipStream_t s);
 hipError_t launch_planar(const PlJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
 hipError_t launch_resample(const RsJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
 hipError_t launch_levels(const LvJob *jobs, uint32_t njobs, const LvFold *folds, uint32_t nfolds, const int32_t *in,
@@ -274,6 +276,11 @@ struct wvg_batch {
     size_t cap_mcjobs = 0, cap_mcstreams = 0;
     uint32_t mc_njobs = 0;
     int mc_plain = 0;  // WVG_MC_PLAIN=1: the strided-store kernel instead of the LDS tile one (A/B)
+    // DSD files opened as PCM (wv_dsdpcm.h): one job per (file, frame tile), built and sent once
+    // per upload; run at the end of every decode, after the DSD fills
+    DpJob *d_dpjobs = nullptr;
+    size_t cap_dpjobs = 0;
+    uint32_t dp_njobs = 0;
     // wvg_batch_planar (wv_planar.h): one job per (convertible file, frame tile).  The jobs
     // depend on fixed_frames, not on the destination, so a table is built and sent once per
     // upload and fixed_frames value, into a staging buffer and a device table of its own:
@@ -606,6 +613,10 @@ static void free_dev(wvg_batch *b) {
     b->d_mcstreams = nullptr;
     b->cap_mcjobs = b->cap_mcstreams = 0;
     b->mc_njobs = 0;
+    hipFree(b->d_dpjobs);
+    b->d_dpjobs = nullptr;
+    b->cap_dpjobs = 0;
+    b->dp_njobs = 0;
     for (auto &t : b->pl) {
         hipFree(t.d_jobs);
         t.d_jobs = nullptr;
@@ -759,6 +770,7 @@ static void fill_info(const FileInfo &fi, wvg_file_info &wi) {
     wi.reduced_channels = fi.out_nch;
     wi.bits_per_sample = fi.bits_per_sample ? (fi.dsd_multiplier > 0 ? fi.bits_per_sample / 8 : fi.bits_per_sample) : 16;
     wi.bytes_per_sample = fi.bytes_per_sample ? fi.bytes_per_sample : 2;
+    if (fi.dsd_as_pcm) wi.bits_per_sample = 24, wi.bytes_per_sample = 3;  // OPEN_DSD_AS_PCM: 24-bit PCM at the byte rate
     wi.version = fi.version;
     wi.mode = fi.mode;
     wi.is_float = fi.is_float;
@@ -766,7 +778,7 @@ static void fill_info(const FileInfo &fi, wvg_file_info &wi) {
     wi.file_format = fi.file_format;
     wi.lossy = ((fi.config_flags & 8) != 0) || (fi.mode & 0x4) != 0 || (fi.open_ok && !(fi.mode & 0x2) && !(fi.mode & 0x4) && fi.lossy_blocks);
     wi.dsd_multiplier = fi.dsd_multiplier;
-    wi.sample_rate = fi.sample_rate ? (fi.dsd_multiplier > 0 ? (int64_t)fi.dsd_multiplier * fi.sample_rate * 8 : fi.sample_rate) : 44100;
+    wi.sample_rate = fi.sample_rate ? (fi.dsd_multiplier > 0 ? (int64_t)fi.dsd_multiplier * fi.sample_rate * (fi.dsd_as_pcm ? 1 : 8) : fi.sample_rate) : 44100;
     wi.total_samples = fi.total_samples;
     wi.out_frames = fi.out_frames;
     wi.out_offset = 0;
@@ -776,7 +788,7 @@ static void fill_info(const FileInfo &fi, wvg_file_info &wi) {
 
 int wvg_probe_file(const uint8_t *file, size_t len, uint32_t open_flags, int chunk_frames, wvg_file_info *info) {
     if ((!file && len) || !info) return WVG_ERR_ARG;
-    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && (open_flags & wvf::OPEN_2CH_MAX)) return WVG_ERR_ARG;
+    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && (open_flags & (wvf::OPEN_2CH_MAX | wvf::OPEN_DSD_AS_PCM))) return WVG_ERR_ARG;
     FramingOutput fo;
     FileInfo fi;
     frame_file(file, len, 0, 0, open_flags, chunk_frames > 0 ? chunk_frames : 4096, fo, fi);
@@ -791,7 +803,7 @@ int wvg_probe_file(const uint8_t *file, size_t len, uint32_t open_flags, int chu
 static int commit_file(wvg_batch *b, FileInfo &fin, size_t len, wvg_file_info *info, int at = -1) {
     wvg_file_info wi;
     fill_info(fin, wi);
-    wi.out_offset = b->out_ints;
+    wi.out_offset = fin.dsd_as_pcm ? fin.dsd_vis_off : b->out_ints;  // (after the staging range)
     wi.header_off = fin.header_off;
     wi.header_len = fin.header_len;
     wi.trailer_off = fin.trailer_off;
@@ -815,7 +827,7 @@ static int commit_file(wvg_batch *b, FileInfo &fin, size_t len, wvg_file_info *i
     b->pcm_off[(size_t)at] = b->pcm_bytes;
     for (int64_t s = 0; s < nvals; s += kFormatSeg) {
         FormatSeg g;
-        g.in_off = (uint64_t)(b->out_ints + s);
+        g.in_off = (uint64_t)(wi.out_offset + s);
         g.out_off = (uint64_t)(b->pcm_bytes + s * wi.bytes_per_sample);
         g.n = (uint32_t)(nvals - s < (int64_t)kFormatSeg ? nvals - s : kFormatSeg);
         g.bps = (uint32_t)wi.bytes_per_sample;
@@ -846,6 +858,8 @@ static int add_file(wvg_batch *b, const uint8_t *file, size_t len, uint32_t open
     if (!b || (!file && len)) return WVG_ERR_ARG;
     // all channels: neither with the channel reduction nor after a seek
     if ((open_flags & wvf::OPEN_ALL_CHANNELS) && ((open_flags & wvf::OPEN_2CH_MAX) || seek_to >= 0)) return WVG_ERR_ARG;
+    // DSD as PCM: neither with all channels nor after a seek
+    if ((open_flags & wvf::OPEN_DSD_AS_PCM) && ((open_flags & wvf::OPEN_ALL_CHANNELS) || seek_to >= 0)) return WVG_ERR_ARG;
     b->uploaded = b->formatted = false;
     size_t base = (b->blob.size() + 15) & ~(size_t)15;
     if (!blob_resize(b, base + len)) {
@@ -979,6 +993,11 @@ static int merge_framed(wvg_batch *b, FramingOutput &f, FileInfo &fi, size_t len
         }
         fi.mc_end += (int64_t)ob;
     }
+    if (fi.dsd_as_pcm) {  // (framed with its staging range at 0: it stays 16-byte aligned)
+        ob = (ob + 3) & ~(uint64_t)3;
+        fi.dsd_stage_off += (int64_t)ob;
+        fi.dsd_vis_off += (int64_t)ob;
+    }
     const uint32_t d0 = (uint32_t)b->fo.descs.size(), i0 = (uint32_t)b->fo.items.size();
     const size_t t0 = (b->fo.tables.size() + 15) & ~(size_t)15;
     for (BlockDesc &d : f.descs) {
@@ -1010,7 +1029,7 @@ static int merge_framed(wvg_batch *b, FramingOutput &f, FileInfo &fi, size_t len
 int wvg_batch_add_files(wvg_batch *b, int n, const uint8_t *const *files, const size_t *lens, uint32_t open_flags,
                         int threads, wvg_file_info *infos, int32_t *indices) {
     if (!b || n < 0 || (n && (!files || !lens))) return WVG_ERR_ARG;
-    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && (open_flags & wvf::OPEN_2CH_MAX)) return WVG_ERR_ARG;
+    if ((open_flags & wvf::OPEN_ALL_CHANNELS) && (open_flags & (wvf::OPEN_2CH_MAX | wvf::OPEN_DSD_AS_PCM))) return WVG_ERR_ARG;
     b->uploaded = b->formatted = false;
     std::vector<size_t> base((size_t)n);
     size_t end = b->blob.size();
@@ -1068,7 +1087,7 @@ int wvg_batch_add_files(wvg_batch *b, int n, const uint8_t *const *files, const 
 int wvg_batch_add_file_wvc(wvg_batch *b, const uint8_t *file, size_t len, const uint8_t *wvc, size_t wvc_len,
                            uint32_t open_flags, wvg_file_info *info) {
     if (!b || (!file && len) || (!wvc && wvc_len)) return WVG_ERR_ARG;
-    if (open_flags & wvf::OPEN_ALL_CHANNELS) return WVG_ERR_ARG;  // (no .wvc for multichannel files)
+    if (open_flags & (wvf::OPEN_ALL_CHANNELS | wvf::OPEN_DSD_AS_PCM)) return WVG_ERR_ARG;  // (no .wvc for either)
     b->uploaded = b->formatted = false;
     const size_t base = (b->blob.size() + 15) & ~(size_t)15;
     const size_t cbase = (base + len + 15) & ~(size_t)15;
@@ -1452,6 +1471,21 @@ int wvg_batch_upload(wvg_batch *b) {
     }
     b->mc_njobs = (uint32_t)mcjobs.size();
     need += al(sizeof(McJob) * mcjobs.size()) + al(sizeof(McStreamDev) * mcstreams.size());
+    // the decimation jobs of the DSD files opened as PCM
+    std::vector<DpJob> dpjobs;
+    for (size_t f = 0; f < b->finfo.size(); f++) {
+        const FileInfo &fi = b->finfo[f];
+        if (!fi.open_ok || !fi.dsd_as_pcm || fi.out_nch < 1 || fi.out_nch > (int)kDpMaxChannels) continue;
+        const uint32_t nch = (uint32_t)fi.out_nch;
+        const uint64_t tf = dp_tile_frames(nch);
+        for (uint64_t f0 = 0; f0 < (uint64_t)fi.out_frames; f0 += tf) {
+            const uint64_t left = (uint64_t)fi.out_frames - f0;
+            dpjobs.push_back({(uint64_t)fi.dsd_stage_off, (uint64_t)fi.dsd_vis_off + f0 * nch, (uint64_t)fi.out_frames, f0,
+                              (uint32_t)(left < tf ? left : tf), nch});
+        }
+    }
+    b->dp_njobs = (uint32_t)dpjobs.size();
+    need += al(sizeof(DpJob) * dpjobs.size());
     build_lane_orders(b);
     for (int t = 0; t < kMaxTermSets; t++)
         need += al(sizeof(uint32_t) * b->ts_list[t].size()) + al(sizeof(uint32_t) * b->ts_lane[t].size());
@@ -1556,6 +1590,10 @@ int wvg_batch_upload(wvg_batch *b) {
         HIPCHK(c, ensure(b->d_mcstreams, b->cap_mcstreams, sizeof(McStreamDev) * mcstreams.size()));
         HIPCHK(c, put(b->d_mcjobs, mcjobs.data(), sizeof(McJob) * mcjobs.size()));
         HIPCHK(c, put(b->d_mcstreams, mcstreams.data(), sizeof(McStreamDev) * mcstreams.size()));
+    }
+    if (b->dp_njobs) {
+        HIPCHK(c, ensure(b->d_dpjobs, b->cap_dpjobs, sizeof(DpJob) * dpjobs.size()));
+        HIPCHK(c, put(b->d_dpjobs, dpjobs.data(), sizeof(DpJob) * dpjobs.size()));
     }
     // the WavpackFormatSamples segments (wvg_batch_format), so a format issues no copy of its own
     HIPCHK(c, ensure(b->d_segs, b->cap_segs, sizeof(FormatSeg) * (b->segs.empty() ? 1 : b->segs.size())));
@@ -1816,6 +1854,9 @@ int wvg_batch_decode(wvg_batch *b, void *stream) {
     // multichannel files: every launch group has joined `s`, the streams' staging ranges are
     // final -- weave them into the visible ranges before `done`
     if (b->mc_njobs) HIPCHK(c, launch_mc(b->d_mcjobs, b->mc_njobs, b->d_mcstreams, b->d_out, b->mc_plain, s));
+    // DSD files opened as PCM: their staging ranges are final (decode kernels, mute fills) --
+    // decimate them into the visible ranges before `done`
+    if (b->dp_njobs) HIPCHK(c, launch_dsdpcm(b->d_dpjobs, b->dp_njobs, b->d_out, s));
     if (b->timing) HIPCHK(c, hipEventRecord(b->tev.back(), s));
     HIPCHK(c, hipEventRecord(b->done, s));
     b->downloaded = false;
@@ -1981,7 +2022,7 @@ static int64_t block_start_frame(const wvg_batch *b, const FileInfo &fi, const w
             return ((int64_t)d.out_off - m.stage_off) / nch;
         }
     nch = wi.reduced_channels ? wi.reduced_channels : 1;
-    return ((int64_t)d.out_off - wi.out_offset) / nch;
+    return ((int64_t)d.out_off - (fi.dsd_as_pcm ? fi.dsd_stage_off : wi.out_offset)) / nch;
 }
 
 static int64_t exception_call_frame_of(const wvg_batch *b, const FileInfo &fi, const wvg_file_info &wi, int64_t kx) {
@@ -2242,7 +2283,7 @@ int wvg_batch_md5(wvg_batch *b, void *stream) {
             j.in_off = (uint64_t)b->infos[i].out_offset;
             j.nvals = (uint64_t)(fi.out_frames * fi.out_nch);
             j.bps = (uint32_t)(fi.md5_bps >= 1 && fi.md5_bps <= 4 ? fi.md5_bps : 2);
-            j.dsd = fi.dsd_multiplier > 0;
+            j.dsd = fi.dsd_bytes();
             j.file = (uint32_t)i;
             j.pad_ = 0;
             jobs.push_back(j);
@@ -2312,7 +2353,7 @@ int wvg_probe_file_md5(const uint8_t *file, size_t len, uint8_t stored[16]) {
 // ---------------------------------------------------------------------------
 static bool pl_convertible(const wvg_batch *b, size_t i) {
     const FileInfo &fi = b->finfo[i];
-    return fi.open_ok && fi.dsd_multiplier == 0 && fi.out_nch >= 1 && fi.out_nch <= (int)kPlMaxChannels &&
+    return fi.open_ok && !fi.dsd_bytes() && fi.out_nch >= 1 && fi.out_nch <= (int)kPlMaxChannels &&
            fi.out_frames >= 0;
 }
 
@@ -2959,6 +3000,42 @@ int wvg_interleave_streams(const int32_t *const *streams, const int32_t *widths,
     return WVG_OK;
 }
 
+// ---- DSD files as 24-bit PCM (WVG_OPEN_DSD_AS_PCM) ----
+int wvg_dsd_pcm_taps(int32_t taps[104], int64_t *sum, int64_t *sum_abs) {
+    if (!taps) return WVG_ERR_ARG;
+    int64_t s = 0, a = 0;
+    for (uint32_t t = 0; t < kDpTaps_n; t++) {
+        taps[t] = kDpTaps[t];
+        s += kDpTaps[t];
+        a += kDpTaps[t] < 0 ? -(int64_t)kDpTaps[t] : kDpTaps[t];
+    }
+    if (sum) *sum = s;
+    if (sum_abs) *sum_abs = a;
+    return WVG_OK;
+}
+
+int wvg_dsd_pcm_tile_frames(int channels) {
+    if (channels < 1 || channels > (int)kDpMaxChannels) return WVG_ERR_ARG;
+    return (int)dp_tile_frames((uint32_t)channels);
+}
+
+int wvg_dsd_pcm_ints(const int32_t *src, int64_t frames, int channels, int32_t *out) {
+    if (channels < 1 || channels > (int)kDpMaxChannels || frames < 0 || (frames && (!src || !out))) return WVG_ERR_ARG;
+    // the kernel's tile code (wv_dsdpcm.h), the workgroup's threads as a loop
+    static constexpr DpTables tables = dp_make_tables();
+    std::vector<uint32_t> win(kDpWinWords);
+    const uint32_t nch = (uint32_t)channels;
+    const uint64_t tf = dp_tile_frames(nch);
+    for (uint64_t f0 = 0; f0 < (uint64_t)frames; f0 += tf) {
+        const uint64_t left = (uint64_t)frames - f0;
+        const DpJob j = {0, f0 * nch, (uint64_t)frames, f0, (uint32_t)(left < tf ? left : tf), nch};
+        if (dp_win_words(j) > kDpWinWords) return WVG_ERR_ARG;  // (cannot happen: kDpWinWords covers every channel count)
+        for (uint32_t tid = 0; tid < kDpThreads; tid++) dp_load(j, src, win.data(), tid, kDpThreads);
+        for (uint32_t tid = 0; tid < kDpThreads; tid++) dp_store(j, win.data(), tables.t, out + j.out_off, tid, kDpThreads);
+    }
+    return WVG_OK;
+}
+
 int wvg_md5_bytes(const uint8_t *data, size_t len, uint8_t digest[16]) {
     if ((!data && len) || !digest) return WVG_ERR_ARG;
     wvmd5::State s;
@@ -2997,6 +3074,7 @@ int wvg_batch_wav(wvg_batch *b, int file, uint8_t *out, int64_t cap, int64_t *wa
     *wav_len = 0;
     *exit_code = 1;
     if (!fi.open_ok) return WVG_OK;  // WvDemo.cs:41-46: error message, no .wav
+    if (fi.dsd_as_pcm) return WVG_ERR_ARG;  // (its stored header describes one-bit audio)
     HIPCHK(c, hipEventSynchronize(b->done));
     if (!b->downloaded) {
         int rc = download_status(b);
@@ -3181,6 +3259,14 @@ static void stream_count_blocks(wvg_stream *s) {
 wvg_stream *wvg_stream_open(wvg_ctx *ctx, const uint8_t *file, size_t len, uint32_t open_flags, int64_t window_frames,
                             wvg_file_info *info) {
     if (!ctx || (!file && len)) return nullptr;
+    if (open_flags & wvf::OPEN_DSD_AS_PCM) {
+        ctx->err = "wvg_stream_open: WVG_OPEN_DSD_AS_PCM is not supported by the stream API";
+        if (info) {
+            memset(info, 0, sizeof(*info));
+            strncpy(info->error, "DSD as PCM: not supported by the stream API", sizeof(info->error) - 1);
+        }
+        return nullptr;
+    }
     if (open_flags & wvf::OPEN_ALL_CHANNELS) {
         ctx->err = "wvg_stream_open: WVG_OPEN_ALL_CHANNELS is not supported by the stream API";
         if (info) {

@@ -97,6 +97,9 @@ constexpr uint32_t OPEN_EXACT_FLOAT = 0x40000000u;
 // open flag beyond the reference: a file of more than two channels opens and every
 // stream of its block groups is decoded (wv_framing.h, wv_mc.h)
 constexpr uint32_t OPEN_ALL_CHANNELS = 0x20000000u;
+// open flag beyond the reference: a DSD file opens as 24-bit PCM at the DSD byte rate; its
+// blocks decode into a staging range and one more kernel decimates them (wv_dsdpcm.h)
+constexpr uint32_t OPEN_DSD_AS_PCM = 0x10000000u;
 constexpr uint32_t OPEN_2CH_MAX = 0x8u;
 
 constexpr int64_t CONFIG_HYBRID_FLAG = 8;

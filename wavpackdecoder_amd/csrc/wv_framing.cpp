@@ -1178,6 +1178,8 @@ bool probe_streams(const uint8_t *file, size_t len, std::vector<int32_t> &widths
 int64_t file_out_extent(const FramingOutput &out, const FileInfo &info, uint64_t out_base_ints) {
     int64_t extent = info.out_frames * info.out_nch;
     if (!info.streams.empty() && info.mc_end - (int64_t)out_base_ints > extent) extent = info.mc_end - (int64_t)out_base_ints;
+    // (a DSD file opened as PCM: the staging range, then the visible one)
+    if (info.dsd_as_pcm) extent += info.dsd_vis_off - (int64_t)out_base_ints;
     for (int64_t k = info.first_desc; k < info.first_desc + info.num_desc; k++) {
         const BlockDesc &d = out.descs[(size_t)k];
         const int64_t e = (int64_t)(d.out_off - out_base_ints) + (int64_t)d.nframes * (int64_t)d.out_nch;
@@ -1659,7 +1661,7 @@ static void frame_streams(const uint8_t *file, size_t len, uint64_t blob_base, u
 void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
                 int chunk, FramingOutput &out, FileInfo &info, int64_t seek_to, const uint8_t *wvc, size_t wvc_len,
                 uint64_t wvc_base) {
-    const uint32_t flags = open_flags & ~OPEN_ALL_CHANNELS;
+    const uint32_t flags = open_flags & ~(OPEN_ALL_CHANNELS | OPEN_DSD_AS_PCM);
     if (open_flags & OPEN_ALL_CHANNELS) {
         std::vector<int32_t> widths;
         int nch = 0;
@@ -1680,7 +1682,23 @@ void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t ou
             return;
         }
     }
+    const size_t z0 = out.zeros.size();
     frame_one(file, len, blob_base, out_base_ints, flags, chunk, out, info, seek_to, wvc, wvc_len, wvc_base, -1, 0);
+    if ((open_flags & OPEN_DSD_AS_PCM) && info.open_ok && info.dsd_multiplier > 0 && seek_to < 0) {
+        // the DSD bytes go to a staging range at the next 16-byte boundary, as long as the
+        // descriptors write (a file that raised the C# exception mid-call keeps that call's);
+        // the visible range of out_frames x out_nch PCM ints follows it
+        const int64_t stage = ((int64_t)out_base_ints + 3) & ~(int64_t)3, pad = stage - (int64_t)out_base_ints;
+        const int64_t extent = file_out_extent(out, info, out_base_ints);
+        for (int64_t k = info.first_desc; k < info.first_desc + info.num_desc; k++) out.descs[(size_t)k].out_off += (uint64_t)pad;
+        for (size_t z = z0; z < out.zeros.size(); z++) out.zeros[z].off += (uint64_t)pad;
+        info.dsd_as_pcm = 1;
+        info.dsd_stage_off = stage;
+        info.dsd_vis_off = stage + extent;
+        // the stored MD5 is over the DSD bytes: this output (3 bytes a value) cannot match it
+        info.md5_bps = 3;
+        info.md5_comparable = 0;
+    }
 }
 
 }  // namespace wvg

@@ -72,6 +72,13 @@ struct FileInfo {
     std::vector<McStream> streams;
     uint32_t channel_mask = 0;
     int64_t mc_end = 0;
+    // OPEN_DSD_AS_PCM on a DSD file: its descriptors write the DSD bytes into a staging range
+    // [dsd_stage_off, dsd_vis_off) of the batch output (ints; the start a multiple of 4) and
+    // its visible range, out_frames x out_nch ints of 24-bit PCM (wv_dsdpcm.h), follows at
+    // dsd_vis_off.  "Is this output DSD bytes" is dsd_multiplier > 0 && !dsd_as_pcm.
+    int32_t dsd_as_pcm = 0;
+    int64_t dsd_stage_off = 0, dsd_vis_off = 0;
+    bool dsd_bytes() const { return dsd_multiplier > 0 && !dsd_as_pcm; }
 };
 
 // DSD fast/high tables live in a side area (bytes) appended per block.
@@ -106,6 +113,10 @@ void apply_meta_jobs(FramingOutput &out, const uint8_t *blob);
 // blocks are the INITIAL_BLOCK ones, out_nch = the stream's width) into a staging range
 // after the file's visible range of out_frames x num_channels ints; info.streams
 // describes them (no seek, no .wvc: the file then does not open).
+// open_flags & OPEN_DSD_AS_PCM on a DSD file: the ordinary walk, its descriptors and zero
+// fills moved to the next multiple of 4 ints at or after out_base_ints (the staging range),
+// the visible range right after everything they write (info.dsd_as_pcm, dsd_stage_off,
+// dsd_vis_off; callers pass neither a seek nor a .wvc with it).  Any other file: no change.
 // wvc (optional): the file's .wvc correction file, whose bytes start at blob
 // offset wvc_base; hybrid blocks then decode exactly (beyond the reference).
 void frame_file(const uint8_t *file, size_t len, uint64_t blob_base, uint64_t out_base_ints, uint32_t open_flags,
