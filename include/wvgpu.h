@@ -599,6 +599,89 @@ int wvg_levels_ints(const int32_t *src, int64_t frames, int channels, int k, uin
                     wvg_channel_levels *out);
 int wvg_levels_tile_frames(int channels);
 
+/* ---- Integrated loudness on the device (beyond the reference): ITU-R BS.1770 / EBU R 128
+ * programme loudness of every file of a decoded batch -- K-weighting, 400 ms blocks every
+ * 100 ms, the absolute and the relative gate -- in float64, 64 bytes per file, with three
+ * kernels per batch (wv_loud.hip) and no PCM downloaded.  What ReplayGain 2.0 and dataset
+ * normalisation are built on; RMS from wvg_batch_levels has neither the weighting nor the
+ * gates.
+ *   A file is measurable by levels' rule (it opened, its output is not DSD bytes -- with
+ * WVG_OPEN_DSD_AS_PCM a DSD file is measured at k = 23 -- and it is not a float file decoded
+ * under WVG_OPEN_EXACT_FLOAT) when also 6,000 <= info.sample_rate <= 3,072,000; other files
+ * get WVG_ERR_OPEN and take no room.  Measured is whatever the int32 output holds over
+ * info.out_frames frames of C = info.reduced_channels interleaved ints, as format / md5 /
+ * planar / levels: a file stopped by an exception has its zeros measured, a
+ * WVG_OPEN_ALL_CHANNELS file is measured over its woven N channels.
+ *   Filter (float64, designed on the host per distinct rate fs; libebur128's re-derivation
+ * of the standard's two biquads, which at 48,000 reproduces BS.1770-4's table to 1e-15):
+ *     shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *            K = tan(pi f0 / fs), Vh = 10^(G/20), Vb = Vh^0.4996667741545416, d = 1 + K/Q + K^2
+ *            b0 = (Vh + Vb K/Q + K^2)/d   b1 = 2 (K^2 - Vh)/d   b2 = (Vh - Vb K/Q + K^2)/d
+ *            a1 = 2 (K^2 - 1)/d           a2 = (1 - K/Q + K^2)/d
+ *     RLB:   f0 = 38.13547087602444, Q = 0.5003270373238773, K = tan(pi f0 / fs), d = 1 + K/Q + K^2
+ *            numerator 1, -2, 1           c1 = 2 (K^2 - 1)/d    c2 = (1 - K/Q + K^2)/d
+ *   Per sample v of a channel (transposed direct form II, this order, fma = fused
+ * multiply-add), x = (double)v * 2^-k with k as planar's (7, 15, 23, 31; exact):
+ *     y1 = fma(b0, x, s1);   s1 = fma(-a1, y1, fma(b1, x, s2));   s2 = fma(-a2, y1, b2 * x);
+ *     y2 = y1 + t1;          t1 = fma(-c1, y2, fma(-2.0, y1, t2)); t2 = fma(-c2, y2, y1);
+ *     e  = fma(y2, y2, e);
+ *   Steps: S = (fs + 5) / 10 frames (100 ms), nsteps = out_frames / S; frames past
+ * nsteps * S are never read.  E[c][j] is e after step j's S frames, e = +0.0 at its first.
+ *   Runs (how the recursive filter is made parallel; a definition, the same on the host):
+ * a run is R = wvg_loudness_run_steps() consecutive steps of one channel, R a build
+ * constant.  The run whose first step is j0 starts the recurrence with s1 = s2 = t1 = t2 =
+ * +0.0 at frame max(0, j0 - 3) * S and discards the energies of those up to three warm-up
+ * steps.  Against the never-restarted filter this leaves out a state that the 38 Hz pole
+ * pair has damped over 0.3 s: about 2^-103, far under float64's rounding.
+ *   Blocks: N = max(0, nsteps - 3); for 0 <= j < N, P_j = acc / (double)(4 * S) with
+ * acc = +0.0 and acc = fma(G_c, ((E[c][j] + E[c][j+1]) + E[c][j+2]) + E[c][j+3], acc) for c
+ * ascending.  Weights G_c: all 1.0 for C <= 2; otherwise the channels take the set bits of
+ * the file's channel mask (wvg_batch_file_streams) in ascending order, bit 3 (LFE) weighs
+ * 0.0, bits 4, 5, 9 and 10 (back and side pairs) 1.41, every other bit and every channel
+ * past the mask's bits 1.0.
+ *   Gating, in the linear domain (no logarithm in this library): ABS = 0x1.f791ec6e1d5b7p-24
+ * (the double nearest 10^((-70 + 0.691) / 10)).  abs_blocks = #{P_j > ABS}, ungated_power =
+ * their mean or 0.0 for none; rel = 0.1 * ungated_power; gated_blocks = #{P_j > ABS and
+ * P_j > rel}, power = their mean or 0.0 for none; max_block_power = max P_j, 0.0 for N = 0.
+ * Each sum over blocks is 64 partial sums (partial l adds P_l, P_(l+64), ... in that order)
+ * joined by a butterfly (l with l ^ 32, then ^ 16, ... ^ 1); a mean is sum / (double)count.
+ * LUFS = -0.691 + 10 log10(power) is the caller's (api.scan_loudness).
+ *   wvg_batch_loudness is ordered exactly as wvg_batch_levels: after wvg_batch_decode, on
+ * `stream` (NULL: the batch's own) behind the upload and the batch's earlier work, and it
+ * returns without waiting (wvg_batch_sync covers it; the next reset / upload waits for it).
+ * The records come down with the call into page-locked memory; tables and coefficients are
+ * built once per upload; the block image (every measurable file's P_j, file after file)
+ * stays on the device and is overwritten by the next call.  WVG_ERR_ARG before an upload.
+ *   wvg_batch_file_loudness, after wvg_batch_sync: WVG_ERR_OPEN for a file that is not
+ * measurable, WVG_ERR_ARG when no wvg_batch_loudness ran since the last upload.
+ * wvg_batch_loudness_blocks: the doubles of the block image; wvg_batch_download_loudness_blocks
+ * waits for the batch's work and copies them (WVG_ERR_SPACE: cap too small).
+ *   Host only: wvg_loudness_filter gives b0 b1 b2 a1 a2 c1 c2 and S for a rate (WVG_ERR_ARG
+ * outside 6,000 .. 3,072,000); wvg_loudness_weights the G_c (channels 1..255);
+ * wvg_loudness_ints runs the kernels' code (wv_loud.h) on the host over `frames` x `channels`
+ * interleaved ints and fills the record (block_offset 0) and the N block powers
+ * (WVG_ERR_SPACE: cap_blocks < N); wvg_loudness_gate runs the gate over any list of block
+ * powers -- an album's, block powers being normalised by their rate -- and fills power,
+ * ungated_power, max_block_power and the three counts (the other fields 0). */
+typedef struct {              /* 64 bytes, one per measurable file */
+    double  power, ungated_power, max_block_power;
+    int64_t blocks, abs_blocks, gated_blocks;
+    int64_t block_offset;     /* the file's first P_j in the block image */
+    int32_t step_frames;      /* S */
+    int32_t channels;
+} wvg_file_loudness;
+
+int wvg_batch_loudness(wvg_batch *b, void *stream);
+int wvg_batch_file_loudness(wvg_batch *b, int file, wvg_file_loudness *out);
+int64_t wvg_batch_loudness_blocks(const wvg_batch *b);
+int wvg_batch_download_loudness_blocks(wvg_batch *b, double *host, int64_t cap);
+int wvg_loudness_filter(int64_t rate, double coef[7], int32_t *step_frames);
+int wvg_loudness_weights(int channels, uint32_t channel_mask, double *w);
+int wvg_loudness_ints(const int32_t *src, int64_t frames, int channels, int k, int64_t rate, uint32_t channel_mask,
+                      wvg_file_loudness *out, double *blocks, int64_t cap_blocks);
+int wvg_loudness_gate(const double *blocks, int64_t n, wvg_file_loudness *out);
+int wvg_loudness_run_steps(void);
+
 /* WvDemo.Main (WvDemo.cs:15-168) for one file of a formatted batch built with
  * chunk_frames 4096: the .wav bytes it writes (stored RIFF header or the
  * synthesized RIFF/fmt/data headers, the PCM, the stored trailer) and its exit

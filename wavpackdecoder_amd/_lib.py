@@ -62,6 +62,11 @@ class WvgFileMd5(ctypes.Structure):
 LEVELS_DTYPE = [("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("sumsq_lo", "<u8"), ("sumsq_hi", "<u8"),
                 ("clipped", "<i8"), ("active", "<i8"), ("first_active", "<i8"), ("last_active", "<i8")]
 
+# wvg_file_loudness (include/wvgpu.h): one 64-byte record per measurable file
+LOUDNESS_DTYPE = [("power", "<f8"), ("ungated_power", "<f8"), ("max_block_power", "<f8"), ("blocks", "<i8"),
+                  ("abs_blocks", "<i8"), ("gated_blocks", "<i8"), ("block_offset", "<i8"), ("step_frames", "<i4"),
+                  ("channels", "<i4")]
+
 
 class WvgFileResult(ctypes.Structure):
     _fields_ = [
@@ -180,6 +185,15 @@ def lib():
         "wvg_batch_file_levels": (i32, [vp, i32, vp, i32]),
         "wvg_levels_ints": (i32, [vp, i64, i32, i32, u32, vp]),
         "wvg_levels_tile_frames": (i32, [i32]),
+        "wvg_batch_loudness": (i32, [vp, vp]),
+        "wvg_batch_file_loudness": (i32, [vp, i32, vp]),
+        "wvg_batch_loudness_blocks": (i64, [vp]),
+        "wvg_batch_download_loudness_blocks": (i32, [vp, vp, i64]),
+        "wvg_loudness_filter": (i32, [i64, vp, ctypes.POINTER(ctypes.c_int32)]),
+        "wvg_loudness_weights": (i32, [i32, u32, vp]),
+        "wvg_loudness_ints": (i32, [vp, i64, i32, i32, i64, u32, vp, vp, i64]),
+        "wvg_loudness_gate": (i32, [vp, i64, vp]),
+        "wvg_loudness_run_steps": (i32, []),
         "wvg_dsd_pcm_taps": (i32, [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "wvg_dsd_pcm_ints": (i32, [vp, i64, i32, vp]),
         "wvg_dsd_pcm_tile_frames": (i32, [i32]),
@@ -214,6 +228,9 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_batch_resample", "wvg_batch_resample_floats", "wvg_batch_file_resample", "wvg_batch_device_resampled",
             "wvg_batch_download_resampled", "wvg_resample_filter", "wvg_resample_float", "wvg_resample_tile_frames",
             "wvg_batch_levels", "wvg_batch_file_levels", "wvg_levels_ints", "wvg_levels_tile_frames",
+            "wvg_batch_loudness", "wvg_batch_file_loudness", "wvg_batch_loudness_blocks",
+            "wvg_batch_download_loudness_blocks", "wvg_loudness_filter", "wvg_loudness_weights", "wvg_loudness_ints",
+            "wvg_loudness_gate", "wvg_loudness_run_steps",
             "wvg_dsd_pcm_taps", "wvg_dsd_pcm_ints", "wvg_dsd_pcm_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of

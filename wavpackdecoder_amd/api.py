@@ -553,6 +553,46 @@ class DecodeBatch:
             self._check(got if got < 0 else _L.WVG_ERR_ARG)
         return out
 
+    def loudness(self, stream=None):
+        """Every measurable file's integrated loudness (ITU-R BS.1770) on the device
+        (wvg_batch_loudness; the definition: include/wvgpu.h), after decode(), on `stream`,
+        without waiting -- sync() covers it."""
+        if not self._uploaded:
+            self.upload()
+        self._check(self._L.wvg_batch_loudness(self._b, stream))
+
+    def file_loudness(self, i: int):
+        """File i's record of the last loudness() (wvg_batch_file_loudness; after sync()): one
+        element of a structured array (_lib.LOUDNESS_DTYPE), or None for a file that is not
+        measurable (levels' rule, or a sample rate outside 6,000 .. 3,072,000)."""
+        out = np.zeros(1, dtype=_L.LOUDNESS_DTYPE)
+        rc = self._L.wvg_batch_file_loudness(self._b, int(i), out.ctypes.data)
+        if rc == _L.WVG_ERR_OPEN:
+            return None
+        self._check(rc)
+        return out[0]
+
+    def download_loudness_blocks(self) -> np.ndarray:
+        """The block image of the last loudness(): every measurable file's block powers P_j,
+        file after file, as float64 (wvg_batch_download_loudness_blocks; waits for it)."""
+        n = self._L.wvg_batch_loudness_blocks(self._b)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        self._check(self._L.wvg_batch_download_loudness_blocks(self._b, out.ctypes.data, out.size))
+        return out[:n]
+
+    def loudness_blocks(self, i: int):
+        """File i's block powers of the last loudness() (float64, one per 400 ms block every
+        100 ms), or None for a file that is not measurable.  Downloads the whole image: a
+        caller that wants many files' takes download_loudness_blocks() once and slices it by
+        the records' block_offset and blocks."""
+        rec = self.file_loudness(i)
+        if rec is None:
+            return None
+        o, n = int(rec["block_offset"]), int(rec["blocks"])
+        return self.download_loudness_blocks()[o: o + n].copy()
+
     def wav(self, i: int):
         """WvDemo.Main for file i (WvDemo.cs:15-168): (exit_code, .wav bytes)."""
         n, rc = ctypes.c_int64(), ctypes.c_int32()
@@ -1038,6 +1078,99 @@ def scan_levels(files, open_flags: int = 0, threshold_q31: int = 0) -> list:
                 "rms_dbfs": [_dbfs(math.sqrt(q / n) / fs) if n else float("-inf") for q in sumsq],
                 "dc": [int(r["sum"]) / n / fs if n else 0.0 for r in rec],
             })
+        return res
+    finally:
+        b.close()
+
+
+def loudness_filter(rate: int):
+    """The K-weighting's coefficients at `rate` (wvg_loudness_filter): (float64 array b0 b1 b2
+    a1 a2 c1 c2, step frames S)."""
+    cf, s = np.zeros(7, dtype=np.float64), ctypes.c_int32()
+    rc = _L.lib().wvg_loudness_filter(int(rate), cf.ctypes.data, ctypes.byref(s))
+    if rc != 0:
+        raise ValueError("rate must be in 6000..3072000")
+    return cf, int(s.value)
+
+
+def loudness_weights(channels: int, channel_mask: int) -> np.ndarray:
+    """The channel weights G_c of a channel count and mask (wvg_loudness_weights)."""
+    if not 1 <= int(channels) <= 255:
+        raise ValueError("channels must be in 1..255")
+    w = np.zeros(int(channels), dtype=np.float64)
+    rc = _L.lib().wvg_loudness_weights(int(channels), int(channel_mask) & 0xFFFFFFFF, w.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_loudness_weights: {rc}")
+    return w
+
+
+def loudness_ints(src: np.ndarray, k: int, rate: int, channel_mask: int = 0):
+    """The loudness kernels' code run on the host (wvg_loudness_ints): `src` is int32 of shape
+    (frames, channels) -- any int alignment -- and full scale is 2^k (k 7 / 15 / 23 / 31).
+    Returns (record, block powers): one element of _lib.LOUDNESS_DTYPE and a float64 array."""
+    a = np.asarray(src)
+    if a.dtype != np.int32:
+        a = a.astype(np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    if not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    frames, nch = a.shape
+    _, s = loudness_filter(rate)
+    n = max(frames // s - 3, 0)
+    rec, blocks = np.zeros(1, dtype=_L.LOUDNESS_DTYPE), np.zeros(max(n, 1), dtype=np.float64)
+    rc = _L.lib().wvg_loudness_ints(a.ctypes.data, frames, nch, int(k), int(rate), int(channel_mask) & 0xFFFFFFFF,
+                                    rec.ctypes.data, blocks.ctypes.data, n)
+    if rc != 0:
+        raise ValueError(f"wvg_loudness_ints: {rc}")
+    return rec[0], blocks[:n]
+
+
+def loudness_gate(blocks):
+    """The gate code over any list of block powers (wvg_loudness_gate), an album's for one:
+    one element of _lib.LOUDNESS_DTYPE with power, ungated_power, max_block_power and the
+    three counts filled."""
+    p = np.ascontiguousarray(np.asarray(blocks, dtype=np.float64).reshape(-1))
+    rec = np.zeros(1, dtype=_L.LOUDNESS_DTYPE)
+    rc = _L.lib().wvg_loudness_gate(p.ctypes.data if p.size else None, p.size, rec.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_loudness_gate: {rc}")
+    return rec[0]
+
+
+def _lufs_dict(rec, target_lufs: float) -> dict:
+    d = {n: (float(rec[n]) if rec.dtype[n].kind == "f" else int(rec[n])) for n in rec.dtype.names}
+    lufs = -0.691 + 10.0 * math.log10(d["power"]) if d["gated_blocks"] > 0 and d["power"] > 0 else float("-inf")
+    d["record"] = rec
+    d["lufs"] = lufs
+    d["gain_db"] = None if lufs == float("-inf") else float(target_lufs) - lufs
+    return d
+
+
+def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album: bool = False) -> list:
+    """Decode `files` and measure each one's integrated loudness on the device: add, upload,
+    decode, loudness and sync, with no PCM formatted or downloaded.  Returns one dict per
+    file, None for a file that is not measurable: the record's fields by name (and `record`
+    itself), `lufs` = -0.691 + 10 log10(power) (-inf when no block passed the gates) and
+    `gain_db` = target_lufs - lufs (None for -inf).  With album=True one more dict follows:
+    the gate (loudness_gate) over the block powers of all measurable files together -- block
+    powers are normalised by their rate, so files of several rates mix."""
+    b = DecodeBatch(SAMPLE_BUFFER_SIZE)
+    try:
+        res, recs = [], []
+        if len(files):
+            idx = b.add_files(files, open_flags)
+            b.decode()
+            b.loudness()
+            b.sync()
+            for i in idx:
+                rec = b.file_loudness(i) if i >= 0 else None
+                recs.append(rec)
+                res.append(None if rec is None else _lufs_dict(rec, target_lufs))
+        if album:
+            img = b.download_loudness_blocks() if any(r is not None for r in recs) else np.zeros(0)
+            parts = [img[int(r["block_offset"]): int(r["block_offset"]) + int(r["blocks"])] for r in recs
+                     if r is not None]
+            res.append(_lufs_dict(loudness_gate(np.concatenate(parts) if parts else np.zeros(0)), target_lufs))
         return res
     finally:
         b.close()

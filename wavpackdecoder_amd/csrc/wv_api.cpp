@@ -22,6 +22,7 @@
 #include "wv_format.h"
 #include "wv_framing.h"
 #include "wv_levels.h"
+#include "wv_loud.h"
 #include "wv_mc.h"
 #include "wv_md5.h"
 #include "wv_planar.h"
@@ -48,6 +49,9 @@ hipError_t launch_planar(const PlJob *jobs, uint32_t njobs, const int32_t *in, f
 hipError_t launch_resample(const RsJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
 hipError_t launch_levels(const LvJob *jobs, uint32_t njobs, const LvFold *folds, uint32_t nfolds, const int32_t *in,
                          LvRecord *partials, LvRecord *out, uint32_t threshold_q31, hipStream_t s);
+hipError_t launch_loudness(const LdFile *files, uint32_t nfiles, const LdRun *runs, uint32_t nruns, uint64_t nblocks,
+                           const double *coefs, const double *weights, const int32_t *in, double *E, double *P,
+                           LdRecord *out, hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
 hipError_t launch_zero_fill(const ZeroSeg *segs, uint32_t nseg, int32_t *out, hipStream_t s);
 hipError_t upload_dsd_ptables();
@@ -347,6 +351,20 @@ struct wvg_batch {
     std::vector<int64_t> lv_rec0;  // per file: its channel-0 record, -1 not measurable
     uint32_t lv_njobs = 0, lv_nfolds = 0;
     bool lv_jobs_sent = false, lv_issued = false;
+    // wvg_batch_loudness (wv_loud.h): one LdFile per measurable file, one LdRun per (file,
+    // channel, run), the filter coefficients per distinct rate and the channel weights,
+    // built and sent once per upload in one table; the step energies, the block image and
+    // the records are shared by the calls as levels' are (each call waits for `done`).
+    uint8_t *d_ldtab = nullptr;   // files | runs | coefficients | weights
+    double *d_ldE = nullptr, *d_ldP = nullptr;
+    LdRecord *d_loud = nullptr;
+    size_t cap_ldtab = 0, cap_ldE = 0, cap_ldP = 0, cap_loud = 0;
+    size_t ld_runs_at = 0, ld_coef_at = 0, ld_w_at = 0;  // byte offsets in d_ldtab
+    PinnedBuf ld_stage, hloud;
+    std::vector<int64_t> ld_rec;  // per file: its record, -1 not measurable
+    uint32_t ld_nfiles = 0, ld_nruns = 0;
+    uint64_t ld_nblocks = 0;
+    bool ld_jobs_sent = false, ld_issued = false;
 };
 
 static int hip_fail(wvg_ctx *c, hipError_t e, const char *what) {
@@ -471,6 +489,63 @@ static uint64_t lv_file_jobs(uint64_t in_off, uint64_t frames, uint32_t nch, uin
     }
     return part + ntiles * nch;
 }
+
+// one file's table entries (wv_loud.h): its LdFile, its runs and its weights.  `e_off`,
+// `blk_off`, `w_off`: where its step energies, block powers and weights start; they advance
+template <class R>
+static LdFile ld_file_jobs(uint32_t file, uint64_t in_off, uint64_t frames, uint32_t nch, uint32_t k, uint32_t S,
+                           uint32_t coef, uint64_t &e_off, uint64_t &blk_off, uint64_t &w_off, R &&run) {
+    LdFile f;
+    f.in_off = in_off;
+    f.e_off = e_off;
+    f.blk_off = blk_off;
+    f.nsteps = (uint32_t)(frames / S);
+    f.nblocks = f.nsteps > kLdWarmSteps ? f.nsteps - kLdWarmSteps : 0u;
+    f.S = S;
+    f.nch = nch;
+    f.k = k;
+    f.coef = coef;
+    f.w_off = w_off;
+    w_off += nch;
+    if (f.nblocks) {
+        e_off += (uint64_t)f.nsteps * nch;
+        blk_off += f.nblocks;
+        // a run's channels are neighbours: the lanes that share a frame share its cache line
+        for (uint32_t j0 = 0; j0 < f.nsteps; j0 += kLdRunSteps)
+            for (uint32_t c = 0; c < nch; c++) {
+                LdRun r;
+                r.file = file;
+                r.ch = c;
+                r.j0 = j0;
+                r.nst = f.nsteps - j0 < kLdRunSteps ? f.nsteps - j0 : kLdRunSteps;
+                run(r);
+            }
+    }
+    return f;
+}
+
+// the two biquads of BS.1770's K-weighting at `rate` (libebur128's re-derivation), in float64
+static void ld_design(int64_t rate, double *cf) {
+    const double pi = 3.14159265358979323846, fs = (double)rate;
+    {
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416);
+        const double d = 1.0 + K / Q + K * K;
+        cf[0] = (Vh + Vb * K / Q + K * K) / d;
+        cf[1] = 2.0 * (K * K - Vh) / d;
+        cf[2] = (Vh - Vb * K / Q + K * K) / d;
+        cf[3] = 2.0 * (K * K - 1.0) / d;
+        cf[4] = (1.0 - K / Q + K * K) / d;
+    }
+    {
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = tan(pi * f0 / fs), d = 1.0 + K / Q + K * K;
+        cf[5] = 2.0 * (K * K - 1.0) / d;
+        cf[6] = (1.0 - K / Q + K * K) / d;
+    }
+}
+
+static uint32_t ld_step_frames(int64_t rate) { return (uint32_t)((rate + 5) / 10); }
 
 extern "C" {
 
@@ -649,6 +724,15 @@ static void free_dev(wvg_batch *b) {
     b->d_lvpart = b->d_levels = nullptr;
     b->cap_lvjobs = b->cap_lvfolds = b->cap_lvpart = b->cap_levels = 0;
     b->lv_jobs_sent = b->lv_issued = false;
+    hipFree(b->d_ldtab);
+    hipFree(b->d_ldE);
+    hipFree(b->d_ldP);
+    hipFree(b->d_loud);
+    b->d_ldtab = nullptr;
+    b->d_ldE = b->d_ldP = nullptr;
+    b->d_loud = nullptr;
+    b->cap_ldtab = b->cap_ldE = b->cap_ldP = b->cap_loud = 0;
+    b->ld_jobs_sent = b->ld_issued = false;
     hipFree(b->d_md5jobs);
     hipFree(b->d_md5);
     b->d_md5jobs = nullptr;
@@ -901,6 +985,7 @@ int wvg_batch_reset(wvg_batch *b) {
     b->framed_dev = b->framed_host = 0;
     b->md5_jobs_sent = b->md5_issued = false;
     b->lv_jobs_sent = b->lv_issued = false;
+    b->ld_jobs_sent = b->ld_issued = false;
     planar_forget(b);
     return WVG_OK;
 }
@@ -1433,6 +1518,7 @@ int wvg_batch_upload(wvg_batch *b) {
     b->formatted = false;
     b->md5_jobs_sent = b->md5_issued = false;
     b->lv_jobs_sent = b->lv_issued = false;
+    b->ld_jobs_sent = b->ld_issued = false;
     planar_forget(b);
     // the blob is followed by 64 B of 0xFF (the reader's past-end fill)
     HIPCHK(c, blob_push(b));  // what the adds have not sent yet
@@ -2928,6 +3014,203 @@ int wvg_levels_ints(const int32_t *src, int64_t frames, int channels, int k, uin
         }
         lv_final(folds[r], lane[0], reinterpret_cast<LvRecord *>(out) + r);
     }
+    return WVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Integrated loudness of the decoded batch on the device (wv_loud.hip)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(wvg_file_loudness) == 64 && sizeof(LdRecord) == 64, "one record is 64 bytes");
+static_assert(offsetof(wvg_file_loudness, ungated_power) == offsetof(LdRecord, ungated_power) &&
+                  offsetof(wvg_file_loudness, max_block_power) == offsetof(LdRecord, max_block_power) &&
+                  offsetof(wvg_file_loudness, blocks) == offsetof(LdRecord, blocks) &&
+                  offsetof(wvg_file_loudness, abs_blocks) == offsetof(LdRecord, abs_blocks) &&
+                  offsetof(wvg_file_loudness, gated_blocks) == offsetof(LdRecord, gated_blocks) &&
+                  offsetof(wvg_file_loudness, block_offset) == offsetof(LdRecord, block_offset) &&
+                  offsetof(wvg_file_loudness, step_frames) == offsetof(LdRecord, step_frames) &&
+                  offsetof(wvg_file_loudness, channels) == offsetof(LdRecord, channels),
+              "LdRecord is wvg_file_loudness");
+static_assert(sizeof(LdFile) % 8 == 0 && sizeof(LdRun) == 16, "the tables are packed behind one another");
+
+// levels' rule and a rate the filter is designed for
+static bool ld_measurable(const wvg_batch *b, size_t i) {
+    const int64_t rate = b->infos[i].sample_rate;
+    return lv_measurable(b, i) && rate >= kLdMinRate && rate <= kLdMaxRate;
+}
+
+// the mask wvg_batch_file_streams reports
+static uint32_t ld_mask(const FileInfo &fi) {
+    return fi.streams.empty() ? 0x5u - (uint32_t)(fi.out_nch == 1 ? 1 : 2) : fi.channel_mask;
+}
+
+int wvg_batch_loudness(wvg_batch *b, void *stream) {
+    if (!b || !b->uploaded) return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    const size_t nf = b->finfo.size();
+    if (!b->ld_jobs_sent) {
+        std::vector<LdFile> files;
+        std::vector<LdRun> runs;
+        std::vector<int64_t> rates;
+        std::vector<double> coefs, weights;
+        b->ld_rec.assign(nf, -1);
+        uint64_t e_off = 0, blk_off = 0, w_off = 0;
+        for (size_t i = 0; i < nf; i++) {
+            if (!ld_measurable(b, i)) continue;
+            const FileInfo &fi = b->finfo[i];
+            const int64_t rate = b->infos[i].sample_rate;
+            const uint32_t S = ld_step_frames(rate);
+            if ((uint64_t)fi.out_frames / S >= 0x7fffffffu || files.size() >= 0x7fffffffu) return WVG_ERR_SPACE;
+            size_t ci = 0;
+            while (ci < rates.size() && rates[ci] != rate) ci++;
+            if (ci == rates.size()) {
+                rates.push_back(rate);
+                coefs.resize(coefs.size() + kLdCoefDoubles, 0.0);
+                ld_design(rate, coefs.data() + ci * kLdCoefDoubles);
+            }
+            weights.resize((size_t)w_off + (size_t)fi.out_nch);
+            ld_weights((uint32_t)fi.out_nch, ld_mask(fi), weights.data() + w_off);
+            b->ld_rec[i] = (int64_t)files.size();
+            files.push_back(ld_file_jobs((uint32_t)files.size(), (uint64_t)b->infos[i].out_offset,
+                                         (uint64_t)fi.out_frames, (uint32_t)fi.out_nch, pl_kind(b, i), S, (uint32_t)ci,
+                                         e_off, blk_off, w_off, [&](const LdRun &r) { runs.push_back(r); }));
+        }
+        if (runs.size() > 0x7fffffffu) return WVG_ERR_SPACE;
+        // (the buffers below may still be in use by a call of the previous upload only
+        // through a caller's stream: the upload's quiesce waited for it)
+        const size_t fb = sizeof(LdFile) * files.size(), rb = sizeof(LdRun) * runs.size();
+        const size_t cb = sizeof(double) * coefs.size(), wb = sizeof(double) * weights.size();
+        const size_t tb = fb + rb + cb + wb, ob = sizeof(LdRecord) * (files.size() ? files.size() : 1);
+        if (!b->ld_stage.resize(tb + 1) || !b->hloud.resize(ob)) return WVG_ERR_SPACE;
+        HIPCHK(c, ensure(b->d_ldtab, b->cap_ldtab, tb ? tb : 1));
+        HIPCHK(c, ensure(b->d_ldE, b->cap_ldE, sizeof(double) * (size_t)(e_off ? e_off : 1)));
+        HIPCHK(c, ensure(b->d_ldP, b->cap_ldP, sizeof(double) * (size_t)(blk_off ? blk_off : 1)));
+        HIPCHK(c, ensure(b->d_loud, b->cap_loud, ob));
+        // on the batch stream, behind the upload's copies; `up` is recorded again so that a
+        // call on a caller's stream waits for the table too (as wvg_batch_levels' jobs)
+        if (tb) {
+            uint8_t *st = b->ld_stage.data();
+            if (fb) memcpy(st, files.data(), fb);
+            if (rb) memcpy(st + fb, runs.data(), rb);
+            if (cb) memcpy(st + fb + rb, coefs.data(), cb);
+            if (wb) memcpy(st + fb + rb + cb, weights.data(), wb);
+            HIPCHK(c, hipMemcpyAsync(b->d_ldtab, st, tb, hipMemcpyHostToDevice, b->stream));
+        }
+        HIPCHK(c, hipEventRecord(b->up, b->stream));
+        b->ld_runs_at = fb;
+        b->ld_coef_at = fb + rb;
+        b->ld_w_at = fb + rb + cb;
+        b->ld_nfiles = (uint32_t)files.size();
+        b->ld_nruns = (uint32_t)runs.size();
+        b->ld_nblocks = blk_off;
+        b->ld_jobs_sent = true;
+    }
+    // after the whole of the last decode, and of whatever ran on the batch since (`done`):
+    // an earlier wvg_batch_loudness has then downloaded its records, so this one may rewrite them
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_loudness(reinterpret_cast<const LdFile *>(b->d_ldtab), b->ld_nfiles,
+                              reinterpret_cast<const LdRun *>(b->d_ldtab + b->ld_runs_at), b->ld_nruns, b->ld_nblocks,
+                              reinterpret_cast<const double *>(b->d_ldtab + b->ld_coef_at),
+                              reinterpret_cast<const double *>(b->d_ldtab + b->ld_w_at), b->d_out, b->d_ldE, b->d_ldP,
+                              b->d_loud, s));
+    if (b->ld_nfiles)
+        HIPCHK(c, hipMemcpyAsync(b->hloud.data(), b->d_loud, sizeof(LdRecord) * (size_t)b->ld_nfiles,
+                                 hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
+    b->ld_issued = true;
+    return WVG_OK;
+}
+
+int wvg_batch_file_loudness(wvg_batch *b, int file, wvg_file_loudness *out) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || !out || !b->ld_issued) return WVG_ERR_ARG;
+    const int64_t r = b->ld_rec[(size_t)file];
+    if (r < 0) return WVG_ERR_OPEN;
+    memcpy(out, b->hloud.data() + sizeof(LdRecord) * (size_t)r, sizeof(LdRecord));
+    return WVG_OK;
+}
+
+int64_t wvg_batch_loudness_blocks(const wvg_batch *b) {
+    if (!b || !b->ld_issued) return WVG_ERR_ARG;
+    return (int64_t)b->ld_nblocks;
+}
+
+int wvg_batch_download_loudness_blocks(wvg_batch *b, double *host, int64_t cap) {
+    if (!b || !b->ld_issued || (!host && b->ld_nblocks)) return WVG_ERR_ARG;
+    if (cap < (int64_t)b->ld_nblocks) return WVG_ERR_SPACE;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamWaitEvent(b->stream, b->done, 0));
+    if (b->ld_nblocks)
+        HIPCHK(c, hipMemcpyAsync(host, b->d_ldP, sizeof(double) * (size_t)b->ld_nblocks, hipMemcpyDeviceToHost,
+                                 b->stream));
+    HIPCHK(c, hipStreamSynchronize(b->stream));
+    return WVG_OK;
+}
+
+int wvg_loudness_filter(int64_t rate, double coef[7], int32_t *step_frames) {
+    if (rate < kLdMinRate || rate > kLdMaxRate) return WVG_ERR_ARG;
+    if (coef) ld_design(rate, coef);
+    if (step_frames) *step_frames = (int32_t)ld_step_frames(rate);
+    return WVG_OK;
+}
+
+int wvg_loudness_weights(int channels, uint32_t channel_mask, double *w) {
+    if (channels < 1 || channels > (int)kLdMaxChannels || !w) return WVG_ERR_ARG;
+    ld_weights((uint32_t)channels, channel_mask, w);
+    return WVG_OK;
+}
+
+int wvg_loudness_run_steps(void) { return (int)kLdRunSteps; }
+
+// the gate kernel's code over `n` block powers, its lanes as loops
+static void ld_gate_host(const LdFile *f, const double *P, uint64_t n, LdRecord *out) {
+    LdGate lane[kLdGateLanes], nxt[kLdGateLanes];
+    LdGate tot[2];
+    double rel = 0.0;
+    for (int pass = 0; pass < 2; pass++) {
+        for (uint32_t l = 0; l < kLdGateLanes; l++) lane[l] = ld_gate_part(P, n, l, kLdGateLanes, rel);
+        for (uint32_t m = kLdGateLanes / 2; m; m >>= 1) {
+            for (uint32_t l = 0; l < kLdGateLanes; l++) nxt[l] = ld_gate_merge(lane[l], lane[l ^ m]);
+            memcpy(lane, nxt, sizeof lane);
+        }
+        tot[pass] = lane[0];
+        rel = 0.1 * ld_gate_mean(tot[0]);
+    }
+    ld_record(f, n, tot[0], tot[1], out);
+}
+
+int wvg_loudness_gate(const double *blocks, int64_t n, wvg_file_loudness *out) {
+    if (n < 0 || (n && !blocks) || !out) return WVG_ERR_ARG;
+    ld_gate_host(nullptr, blocks, (uint64_t)n, reinterpret_cast<LdRecord *>(out));
+    return WVG_OK;
+}
+
+int wvg_loudness_ints(const int32_t *src, int64_t frames, int channels, int k, int64_t rate, uint32_t channel_mask,
+                      wvg_file_loudness *out, double *blocks, int64_t cap_blocks) {
+    if (channels < 1 || channels > (int)kLdMaxChannels || frames < 0 || (k != 7 && k != 15 && k != 23 && k != 31) ||
+        rate < kLdMinRate || rate > kLdMaxRate || (frames && !src) || !out || cap_blocks < 0 || (cap_blocks && !blocks))
+        return WVG_ERR_ARG;
+    const uint32_t S = ld_step_frames(rate);
+    if ((uint64_t)frames / S >= 0x7fffffffu) return WVG_ERR_SPACE;
+    double cf[kLdCoefDoubles] = {0};
+    ld_design(rate, cf);
+    std::vector<double> w((size_t)channels);
+    ld_weights((uint32_t)channels, channel_mask, w.data());
+    // the kernels' code (wv_loud.h), their threads as loops
+    std::vector<LdRun> runs;
+    uint64_t e_n = 0, blk_n = 0, w_n = 0;
+    const LdFile f = ld_file_jobs(0, 0, (uint64_t)frames, (uint32_t)channels, (uint32_t)k, S, 0, e_n, blk_n, w_n,
+                                  [&](const LdRun &r) { runs.push_back(r); });
+    if ((int64_t)blk_n > cap_blocks) return WVG_ERR_SPACE;
+    std::vector<double> E((size_t)e_n);
+    for (const LdRun &r : runs) ld_run(f, r, cf, src, E.data());
+    for (uint64_t idx = 0; idx < blk_n; idx++) {
+        const LdFile &g = (&f)[ld_find_file(&f, 1, idx)];
+        blocks[idx] = ld_block(g, E.data() + g.e_off, w.data() + g.w_off, (uint32_t)(idx - g.blk_off));
+    }
+    ld_gate_host(&f, blocks, blk_n, reinterpret_cast<LdRecord *>(out));
     return WVG_OK;
 }
 
