@@ -599,6 +599,82 @@ int wvg_levels_ints(const int32_t *src, int64_t frames, int channels, int k, uin
                     wvg_channel_levels *out);
 int wvg_levels_tile_frames(int channels);
 
+/* ---- True peak on the device (beyond the reference): ITU-R BS.1770 Annex 2's maximum of
+ * the oversampled signal, per channel, as exact integers, 48 bytes per channel, with two
+ * kernels per batch (wv_tpeak.hip) and no PCM downloaded.  What ReplayGain 2.0 and EBU R 128
+ * pair with programme loudness: whether a gain clips.  wvg_batch_levels' min / max is the
+ * sample peak; a full-scale sine at fs/4 sampled 45 degrees off its crests has a sample peak
+ * of -3.01 dBFS and a true peak of 0 dBTP.
+ *   A file is measurable by levels' rule, unchanged: it opened, its output is not DSD bytes
+ * (with WVG_OPEN_DSD_AS_PCM a DSD file is measured at k = 23) and it is not a float file
+ * decoded under WVG_OPEN_EXACT_FLOAT.  Measured is whatever the int32 output holds over
+ * info.out_frames frames of C = info.reduced_channels interleaved ints at info.out_offset;
+ * a WVG_OPEN_ALL_CHANNELS file is measured over its woven N channels.  k is planar's
+ * full-scale exponent (7, 15, 23, 31; 23 for a float file without the exact flag).
+ *   Oversampling factor O: `oversample` is 0, 1, 2 or 4 (anything else: WVG_ERR_ARG).  With 0
+ * each file takes its own from info.sample_rate: 4 below 96,000, 2 below 192,000, 1 from
+ * there on (Annex 2's "4x at 48 kHz, proportionally less above"; libebur128's rule; a DSD
+ * file as PCM at 352,800 Hz gets 1).  wvg_true_peak_oversample(rate) reports it.
+ *   Filter: 12 taps per phase, as Annex 2's 48-tap filter has; the project's own
+ * Hann-windowed sinc (lpw = 6, rolloff 1.0), evaluated in float64.  For quarter-phase q =
+ * 0..3 and tap j = 0..11: t = (j - 5) - q/4, h_q[j] = sinc(pi t) * cos^2(pi t / 12) (sinc(0) =
+ * 1; 0 for |t| >= 6).  Phase 0 is the identity; for q >= 1, c_q[j] = round-to-nearest(h_q[j] /
+ * sum_j h_q[j] * 2^24):
+ *     q=0: 0 0 0 0 0 16777216 0 0 0 0 0 0
+ *     q=1: -27363 173728 -504882 1159730 -2707526 15032977 4840980 -1734883 775827 -310666 82102 -2808
+ *     q=2: -16528 173638 -564942 1343293 -3036105 10489252 10489252 -3036105 1343293 -564942 173638 -16528
+ *     q=3: row q=1 reversed
+ * Every row sums to exactly 2^24 (DC gain 1); the largest sum of |c| is row 2's, 31,247,516 =
+ * 1.8625 * 2^24; no scaled tap is closer than 0.038 to a rounding boundary, so any libm gives
+ * these integers.  O = 4 uses rows 0, 1, 2, 3; O = 2 rows 0 and 2; O = 1 row 0.
+ *   Outputs: x[m] is the channel's value at frame m for 0 <= m < F, else 0.  For 0 <= n < F
+ * and phase index p = 0..O-1 (row q = p * 4/O): y[n][p] = sum_{j=0..11} c_q[j] * x[n - 5 + j],
+ * an exact integer in units of 2^-(k+24) of full scale; |y| <= 2^31 * 1.8625 * 2^24 < 2^56 for
+ * any int32 input, INT32_MIN included, so no sum leaves int64 in any order.  The interval
+ * before frame 0 is not interpolated.
+ *   One record per (measurable file, channel):
+ *     true_peak          max |y[n][p]|; 0 for no frames
+ *     true_peak_pos      n * O + p of the first output that attains it; -1 for no frames
+ *     overs              outputs with |y| > 2^(k+24): above 0 dBTP
+ *     sample_peak        max |x[m]| (2^31 for INT32_MIN)
+ *     sample_peak_frame  first frame that attains it; -1 for no frames
+ *     oversample, k      the O used and the depth
+ * "First" makes the fold (larger magnitude, then smaller position): associative and
+ * commutative, so tile order and butterfly order cannot change a record.  An all-zero
+ * channel has peak 0 at position 0.
+ *   wvg_batch_true_peak is ordered exactly as wvg_batch_levels: after wvg_batch_decode, on
+ * `stream` (NULL: the batch's own) behind the upload and the batch's earlier work, and it
+ * returns without waiting (wvg_batch_sync covers it; the next reset / upload waits for it).
+ * The records come down with the call into page-locked memory; every partial and record is
+ * written by every call; the job tables are built once per upload.  Calls with other
+ * `oversample` values may be queued back to back: the last one defines what
+ * wvg_batch_file_true_peak returns.  WVG_ERR_ARG before an upload.
+ *   wvg_batch_file_true_peak, after wvg_batch_sync: returns C and fills min(C, cap_channels)
+ * records; WVG_ERR_OPEN for a file that is not measurable; WVG_ERR_ARG when no
+ * wvg_batch_true_peak ran since the last upload.
+ *   Host only: wvg_true_peak_taps gives the four rows; wvg_true_peak_tile_frames the frames
+ * of one tile for a channel count (1..255); wvg_true_peak_ints runs the kernels' tile and
+ * combine code (wv_tpeak.h) on the host over `frames` x `channels` interleaved ints
+ * (channels 1..255, k one of 7 / 15 / 23 / 31, oversample 1, 2 or 4): `channels` records at
+ * `out`. */
+typedef struct {              /* 48 bytes, one per (measurable file, channel) */
+    int64_t true_peak;        /* max |y[n][p]|; 0 for no frames */
+    int64_t true_peak_pos;    /* n * O + p of the first output that attains it; -1 for no frames */
+    int64_t overs;            /* outputs with |y| > 2^(k+24): above 0 dBTP */
+    int64_t sample_peak;      /* max |x[m]| (2^31 for INT32_MIN) */
+    int64_t sample_peak_frame;/* first frame that attains it; -1 for no frames */
+    int32_t oversample;       /* the O used */
+    int32_t k;
+} wvg_channel_true_peak;
+
+int wvg_batch_true_peak(wvg_batch *b, int oversample, void *stream);
+int wvg_batch_file_true_peak(wvg_batch *b, int file, wvg_channel_true_peak *out, int cap_channels);
+int wvg_true_peak_taps(int32_t taps[48]);
+int wvg_true_peak_oversample(int64_t rate);
+int wvg_true_peak_tile_frames(int channels);
+int wvg_true_peak_ints(const int32_t *src, int64_t frames, int channels, int k, int oversample,
+                       wvg_channel_true_peak *out);
+
 /* ---- Integrated loudness on the device (beyond the reference): ITU-R BS.1770 / EBU R 128
  * programme loudness of every file of a decoded batch -- K-weighting, 400 ms blocks every
  * 100 ms, the absolute and the relative gate -- in float64, 64 bytes per file, with three

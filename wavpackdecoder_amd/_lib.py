@@ -62,6 +62,10 @@ class WvgFileMd5(ctypes.Structure):
 LEVELS_DTYPE = [("min", "<i4"), ("max", "<i4"), ("sum", "<i8"), ("sumsq_lo", "<u8"), ("sumsq_hi", "<u8"),
                 ("clipped", "<i8"), ("active", "<i8"), ("first_active", "<i8"), ("last_active", "<i8")]
 
+# wvg_channel_true_peak (include/wvgpu.h): one 48-byte record per (measurable file, channel)
+TRUE_PEAK_DTYPE = [("true_peak", "<i8"), ("true_peak_pos", "<i8"), ("overs", "<i8"), ("sample_peak", "<i8"),
+                   ("sample_peak_frame", "<i8"), ("oversample", "<i4"), ("k", "<i4")]
+
 # wvg_file_loudness (include/wvgpu.h): one 64-byte record per measurable file
 LOUDNESS_DTYPE = [("power", "<f8"), ("ungated_power", "<f8"), ("max_block_power", "<f8"), ("blocks", "<i8"),
                   ("abs_blocks", "<i8"), ("gated_blocks", "<i8"), ("block_offset", "<i8"), ("step_frames", "<i4"),
@@ -185,6 +189,12 @@ def lib():
         "wvg_batch_file_levels": (i32, [vp, i32, vp, i32]),
         "wvg_levels_ints": (i32, [vp, i64, i32, i32, u32, vp]),
         "wvg_levels_tile_frames": (i32, [i32]),
+        "wvg_batch_true_peak": (i32, [vp, i32, vp]),
+        "wvg_batch_file_true_peak": (i32, [vp, i32, vp, i32]),
+        "wvg_true_peak_taps": (i32, [vp]),
+        "wvg_true_peak_oversample": (i32, [i64]),
+        "wvg_true_peak_tile_frames": (i32, [i32]),
+        "wvg_true_peak_ints": (i32, [vp, i64, i32, i32, i32, vp]),
         "wvg_batch_loudness": (i32, [vp, vp]),
         "wvg_batch_file_loudness": (i32, [vp, i32, vp]),
         "wvg_batch_loudness_blocks": (i64, [vp]),
@@ -228,6 +238,8 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_batch_resample", "wvg_batch_resample_floats", "wvg_batch_file_resample", "wvg_batch_device_resampled",
             "wvg_batch_download_resampled", "wvg_resample_filter", "wvg_resample_float", "wvg_resample_tile_frames",
             "wvg_batch_levels", "wvg_batch_file_levels", "wvg_levels_ints", "wvg_levels_tile_frames",
+            "wvg_batch_true_peak", "wvg_batch_file_true_peak", "wvg_true_peak_taps", "wvg_true_peak_oversample",
+            "wvg_true_peak_tile_frames", "wvg_true_peak_ints",
             "wvg_batch_loudness", "wvg_batch_file_loudness", "wvg_batch_loudness_blocks",
             "wvg_batch_download_loudness_blocks", "wvg_loudness_filter", "wvg_loudness_weights", "wvg_loudness_ints",
             "wvg_loudness_gate", "wvg_loudness_run_steps",

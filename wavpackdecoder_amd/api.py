@@ -553,6 +553,33 @@ class DecodeBatch:
             self._check(got if got < 0 else _L.WVG_ERR_ARG)
         return out
 
+    def true_peak(self, oversample: int = 0, stream=None):
+        """Every measurable file's per-channel true peak (ITU-R BS.1770 Annex 2) on the device
+        (wvg_batch_true_peak; the definition: include/wvgpu.h), after decode(), on `stream`,
+        without waiting -- sync() covers it.  oversample: 1, 2 or 4, or 0 for each file's own
+        factor by its sample rate (4 below 96,000, 2 below 192,000, else 1)."""
+        oversample = int(oversample)
+        if oversample not in (0, 1, 2, 4):
+            raise ValueError("oversample must be 0, 1, 2 or 4")
+        if not self._uploaded:
+            self.upload()
+        self._check(self._L.wvg_batch_true_peak(self._b, oversample, stream))
+
+    def file_true_peak(self, i: int):
+        """File i's records of the last true_peak() (wvg_batch_file_true_peak; after sync()): a
+        structured array (_lib.TRUE_PEAK_DTYPE) of one record per channel, or None for a file
+        that is not measurable (levels' rule)."""
+        n = self._L.wvg_batch_file_true_peak(self._b, int(i), None, 0)
+        if n == _L.WVG_ERR_OPEN:
+            return None
+        if n < 0:
+            self._check(n)
+        out = np.zeros(n, dtype=_L.TRUE_PEAK_DTYPE)
+        got = self._L.wvg_batch_file_true_peak(self._b, int(i), out.ctypes.data, n)
+        if got != n:
+            self._check(got if got < 0 else _L.WVG_ERR_ARG)
+        return out
+
     def loudness(self, stream=None):
         """Every measurable file's integrated loudness (ITU-R BS.1770) on the device
         (wvg_batch_loudness; the definition: include/wvgpu.h), after decode(), on `stream`,
@@ -1083,6 +1110,94 @@ def scan_levels(files, open_flags: int = 0, threshold_q31: int = 0) -> list:
         b.close()
 
 
+def true_peak_taps() -> np.ndarray:
+    """The interpolator's integer taps (wvg_true_peak_taps): int32 of shape (4, 12), row q the
+    quarter-phase q, scaled by 2^24."""
+    t = np.zeros(48, dtype=np.int32)
+    rc = _L.lib().wvg_true_peak_taps(t.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_true_peak_taps: {rc}")
+    return t.reshape(4, 12)
+
+
+def true_peak_oversample(rate: int) -> int:
+    """The oversampling factor a sample rate gets (wvg_true_peak_oversample): 4, 2 or 1."""
+    return int(_L.lib().wvg_true_peak_oversample(int(rate)))
+
+
+def true_peak_tile_frames(channels: int) -> int:
+    """Frames of one tile of the true-peak kernel for a channel count (wv_tpeak.h)."""
+    t = _L.lib().wvg_true_peak_tile_frames(int(channels))
+    if t < 0:
+        raise ValueError("channels must be in 1..255")
+    return int(t)
+
+
+def true_peak_ints(src: np.ndarray, k: int, oversample: int) -> np.ndarray:
+    """The true-peak kernels' tile and combine code run on the host (wvg_true_peak_ints):
+    `src` is int32 of shape (frames, channels) -- any int alignment --, full scale is 2^k (k
+    7 / 15 / 23 / 31) and oversample 1, 2 or 4.  Returns one record (_lib.TRUE_PEAK_DTYPE)
+    per channel."""
+    a = np.asarray(src)
+    if a.dtype != np.int32:
+        a = a.astype(np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    if not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    frames, nch = a.shape
+    out = np.zeros(max(nch, 1), dtype=_L.TRUE_PEAK_DTYPE)
+    rc = _L.lib().wvg_true_peak_ints(a.ctypes.data, frames, nch, int(k), int(oversample), out.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_true_peak_ints: {rc}")
+    return out[:nch]
+
+
+def _true_peak_dict(rec, info) -> dict:
+    k, n = int(rec[0]["k"]), int(info.out_frames)
+    fs, rate = float(1 << (k + 24)), float(info.sample_rate)
+    tp = [int(r["true_peak"]) / fs for r in rec]
+    dbtp = [_dbfs(x) for x in tp]
+    return {
+        "records": rec, "k": k, "out_frames": n,
+        "true_peak": tp, "dbtp": dbtp,
+        "sample_peak_dbfs": [_dbfs(int(r["sample_peak"]) / float(1 << k)) for r in rec],
+        "overs": [int(r["overs"]) for r in rec],
+        "position_s": [int(r["true_peak_pos"]) / int(r["oversample"]) / rate if int(r["true_peak_pos"]) >= 0 and rate > 0
+                       else None for r in rec],
+        "max_dbtp": max(dbtp),
+    }
+
+
+def scan_true_peak(files, open_flags: int = 0, oversample: int = 0) -> list:
+    """Decode `files` and measure each channel's true peak on the device: add, upload, decode,
+    true_peak and sync, with no PCM formatted or downloaded (48 bytes a channel come back).
+    Returns one dict per file, None for a file that is not measurable:
+      records     the structured array of DecodeBatch.file_true_peak (exact integers)
+      k           full scale is 2^k
+      out_frames  the frames measured
+      true_peak, dbtp, sample_peak_dbfs, overs, position_s   per channel: peak / 2^(k+24) as
+                  a float, that in dB (-inf for silence), the sample peak in dB, the outputs
+                  above 0 dBTP, and (pos / O) / sample_rate in seconds (None for no frames)
+      max_dbtp    the file's maximum of dbtp
+    The floats are conveniences derived here in floating point; they are not part of the
+    exact contract the records keep."""
+    if not len(files):
+        return []
+    b = DecodeBatch(SAMPLE_BUFFER_SIZE)
+    try:
+        idx = b.add_files(files, open_flags)
+        b.decode()
+        b.true_peak(oversample)
+        b.sync()
+        res = []
+        for i in idx:
+            rec = b.file_true_peak(i) if i >= 0 else None
+            res.append(None if rec is None else _true_peak_dict(rec, b.infos[i]))
+        return res
+    finally:
+        b.close()
+
+
 def loudness_filter(rate: int):
     """The K-weighting's coefficients at `rate` (wvg_loudness_filter): (float64 array b0 b1 b2
     a1 a2 c1 c2, step frames S)."""
@@ -1146,31 +1261,48 @@ def _lufs_dict(rec, target_lufs: float) -> dict:
     return d
 
 
-def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album: bool = False) -> list:
+def _clip_safe(d: dict, tp_dbtp: float) -> None:
+    d["true_peak_dbtp"] = tp_dbtp
+    d["clip_safe_gain_db"] = None if d["gain_db"] is None else min(d["gain_db"], -tp_dbtp)
+
+
+def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album: bool = False,
+                  true_peak: bool = False) -> list:
     """Decode `files` and measure each one's integrated loudness on the device: add, upload,
     decode, loudness and sync, with no PCM formatted or downloaded.  Returns one dict per
     file, None for a file that is not measurable: the record's fields by name (and `record`
     itself), `lufs` = -0.691 + 10 log10(power) (-inf when no block passed the gates) and
     `gain_db` = target_lufs - lufs (None for -inf).  With album=True one more dict follows:
     the gate (loudness_gate) over the block powers of all measurable files together -- block
-    powers are normalised by their rate, so files of several rates mix."""
+    powers are normalised by their rate, so files of several rates mix.
+    With true_peak=True the true peak (DecodeBatch.true_peak, each file's own oversampling
+    factor) is queued on the same decode, and each dict gains `true_peak_dbtp`, the maximum
+    over the file's channels, and `clip_safe_gain_db` = min(gain_db, -true_peak_dbtp) (None
+    where gain_db is None); the album dict gains the maximum over the files."""
     b = DecodeBatch(SAMPLE_BUFFER_SIZE)
     try:
-        res, recs = [], []
+        res, recs, peaks = [], [], []
         if len(files):
             idx = b.add_files(files, open_flags)
             b.decode()
             b.loudness()
+            if true_peak:
+                b.true_peak(0)
             b.sync()
             for i in idx:
                 rec = b.file_loudness(i) if i >= 0 else None
                 recs.append(rec)
                 res.append(None if rec is None else _lufs_dict(rec, target_lufs))
+                if true_peak and rec is not None:
+                    peaks.append(_true_peak_dict(b.file_true_peak(i), b.infos[i])["max_dbtp"])
+                    _clip_safe(res[-1], peaks[-1])
         if album:
             img = b.download_loudness_blocks() if any(r is not None for r in recs) else np.zeros(0)
             parts = [img[int(r["block_offset"]): int(r["block_offset"]) + int(r["blocks"])] for r in recs
                      if r is not None]
             res.append(_lufs_dict(loudness_gate(np.concatenate(parts) if parts else np.zeros(0)), target_lufs))
+            if true_peak:
+                _clip_safe(res[-1], max(peaks) if peaks else float("-inf"))
         return res
     finally:
         b.close()

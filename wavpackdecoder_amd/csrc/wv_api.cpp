@@ -22,6 +22,7 @@
 #include "wv_format.h"
 #include "wv_framing.h"
 #include "wv_levels.h"
+#include "wv_tpeak.h"
 #include "wv_loud.h"
 #include "wv_mc.h"
 #include "wv_md5.h"
@@ -49,6 +50,8 @@ hipError_t launch_planar(const PlJob *jobs, uint32_t njobs, const int32_t *in, f
 hipError_t launch_resample(const RsJob *jobs, uint32_t njobs, const int32_t *in, float *img, hipStream_t s);
 hipError_t launch_levels(const LvJob *jobs, uint32_t njobs, const LvFold *folds, uint32_t nfolds, const int32_t *in,
                          LvRecord *partials, LvRecord *out, uint32_t threshold_q31, hipStream_t s);
+hipError_t launch_true_peak(const TpJob *jobs, uint32_t njobs, const TpFold *folds, uint32_t nfolds, const int32_t *in,
+                            TpRecord *partials, TpRecord *out, uint32_t oversample, hipStream_t s);
 hipError_t launch_loudness(const LdFile *files, uint32_t nfiles, const LdRun *runs, uint32_t nruns, uint64_t nblocks,
                            const double *coefs, const double *weights, const int32_t *in, double *E, double *P,
                            LdRecord *out, hipStream_t s);
@@ -351,6 +354,17 @@ struct wvg_batch {
     std::vector<int64_t> lv_rec0;  // per file: its channel-0 record, -1 not measurable
     uint32_t lv_njobs = 0, lv_nfolds = 0;
     bool lv_jobs_sent = false, lv_issued = false;
+    // wvg_batch_true_peak (wv_tpeak.h): levels' arrangement.  The oversampling factor is a
+    // kernel argument (0: each job's own, from its file's rate), so calls with other factors
+    // share the tables, the partials, the records and their landing area.
+    TpJob *d_tpjobs = nullptr;
+    TpFold *d_tpfolds = nullptr;
+    TpRecord *d_tppart = nullptr, *d_tpeak = nullptr;
+    size_t cap_tpjobs = 0, cap_tpfolds = 0, cap_tppart = 0, cap_tpeak = 0;
+    PinnedBuf tp_stage, htpeak;
+    std::vector<int64_t> tp_rec0;  // per file: its channel-0 record, -1 not measurable
+    uint32_t tp_njobs = 0, tp_nfolds = 0;
+    bool tp_jobs_sent = false, tp_issued = false;
     // wvg_batch_loudness (wv_loud.h): one LdFile per measurable file, one LdRun per (file,
     // channel, run), the filter coefficients per distinct rate and the channel weights,
     // built and sent once per upload in one table; the step energies, the block image and
@@ -485,6 +499,36 @@ static uint64_t lv_file_jobs(uint64_t in_off, uint64_t frames, uint32_t nch, uin
         f.part = part + c;
         f.ntiles = (uint32_t)ntiles;
         f.nch = nch;
+        fold(f);
+    }
+    return part + ntiles * nch;
+}
+
+// the tiles of one file (wv_tpeak.h) and its folds; `part`: its first record in the partials
+template <class J, class F>
+static uint64_t tp_file_jobs(uint64_t in_off, uint64_t frames, uint32_t nch, uint32_t k, uint32_t o_rate,
+                             uint64_t part, J &&job, F &&fold) {
+    const uint64_t tf = tp_tile_frames(nch), ntiles = (frames + tf - 1) / tf;
+    for (uint64_t t = 0; t < ntiles; t++) {
+        const uint64_t f0 = t * tf, left = frames - f0;
+        TpJob j;
+        j.in_off = in_off + f0 * nch;
+        j.frame0 = f0;
+        j.frames = frames;
+        j.part = part + t * nch;
+        j.nvalid = (uint32_t)(left < tf ? left : tf);
+        j.nch = nch;
+        j.k = k;
+        j.o_rate = o_rate;
+        job(j);
+    }
+    for (uint32_t c = 0; c < nch; c++) {
+        TpFold f;
+        f.part = part + c;
+        f.ntiles = (uint32_t)ntiles;
+        f.nch = nch;
+        f.k = k;
+        f.o_rate = o_rate;
         fold(f);
     }
     return part + ntiles * nch;
@@ -724,6 +768,15 @@ static void free_dev(wvg_batch *b) {
     b->d_lvpart = b->d_levels = nullptr;
     b->cap_lvjobs = b->cap_lvfolds = b->cap_lvpart = b->cap_levels = 0;
     b->lv_jobs_sent = b->lv_issued = false;
+    hipFree(b->d_tpjobs);
+    hipFree(b->d_tpfolds);
+    hipFree(b->d_tppart);
+    hipFree(b->d_tpeak);
+    b->d_tpjobs = nullptr;
+    b->d_tpfolds = nullptr;
+    b->d_tppart = b->d_tpeak = nullptr;
+    b->cap_tpjobs = b->cap_tpfolds = b->cap_tppart = b->cap_tpeak = 0;
+    b->tp_jobs_sent = b->tp_issued = false;
     hipFree(b->d_ldtab);
     hipFree(b->d_ldE);
     hipFree(b->d_ldP);
@@ -985,6 +1038,7 @@ int wvg_batch_reset(wvg_batch *b) {
     b->framed_dev = b->framed_host = 0;
     b->md5_jobs_sent = b->md5_issued = false;
     b->lv_jobs_sent = b->lv_issued = false;
+    b->tp_jobs_sent = b->tp_issued = false;
     b->ld_jobs_sent = b->ld_issued = false;
     planar_forget(b);
     return WVG_OK;
@@ -1518,6 +1572,7 @@ int wvg_batch_upload(wvg_batch *b) {
     b->formatted = false;
     b->md5_jobs_sent = b->md5_issued = false;
     b->lv_jobs_sent = b->lv_issued = false;
+    b->tp_jobs_sent = b->tp_issued = false;
     b->ld_jobs_sent = b->ld_issued = false;
     planar_forget(b);
     // the blob is followed by 64 B of 0xFF (the reader's past-end fill)
@@ -3013,6 +3068,159 @@ int wvg_levels_ints(const int32_t *src, int64_t frames, int channels, int k, uin
             lane.swap(lnxt);
         }
         lv_final(folds[r], lane[0], reinterpret_cast<LvRecord *>(out) + r);
+    }
+    return WVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Per-channel true peak of the decoded batch on the device (wv_tpeak.hip)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(wvg_channel_true_peak) == 48 && sizeof(TpRecord) == 48, "one record is 48 bytes");
+static_assert(offsetof(wvg_channel_true_peak, true_peak_pos) == offsetof(TpRecord, true_peak_pos) &&
+                  offsetof(wvg_channel_true_peak, overs) == offsetof(TpRecord, overs) &&
+                  offsetof(wvg_channel_true_peak, sample_peak) == offsetof(TpRecord, sample_peak) &&
+                  offsetof(wvg_channel_true_peak, sample_peak_frame) == offsetof(TpRecord, sample_peak_frame) &&
+                  offsetof(wvg_channel_true_peak, oversample) == offsetof(TpRecord, oversample) &&
+                  offsetof(wvg_channel_true_peak, k) == offsetof(TpRecord, k),
+              "TpRecord is wvg_channel_true_peak");
+
+// the tile of every channel count fits the kernel's LDS array, a discarded step's reads included
+static bool tp_tile_fits(uint32_t nch) {
+    return nch * tp_pitch(nch) + 2u * kTpUnroll + kTpHalo + 1u <= kTpLdsInts;
+}
+
+int wvg_batch_true_peak(wvg_batch *b, int oversample, void *stream) {
+    if (!b || !b->uploaded || (oversample != 0 && oversample != 1 && oversample != 2 && oversample != 4))
+        return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    const size_t nf = b->finfo.size();
+    if (!b->tp_jobs_sent) {
+        std::vector<TpJob> jobs;
+        std::vector<TpFold> folds;
+        b->tp_rec0.assign(nf, -1);
+        uint64_t part = 0;
+        for (size_t i = 0; i < nf; i++) {
+            if (!lv_measurable(b, i)) continue;  // levels' rule
+            const FileInfo &fi = b->finfo[i];
+            if (!tp_tile_fits((uint32_t)fi.out_nch) ||
+                (uint64_t)fi.out_frames / tp_tile_frames((uint32_t)fi.out_nch) >= 0x7fffffffu)
+                return WVG_ERR_SPACE;
+            b->tp_rec0[i] = (int64_t)folds.size();
+            part = tp_file_jobs((uint64_t)b->infos[i].out_offset, (uint64_t)fi.out_frames, (uint32_t)fi.out_nch,
+                                pl_kind(b, i), tp_oversample((int64_t)b->infos[i].sample_rate), part,
+                                [&](const TpJob &j) { jobs.push_back(j); }, [&](const TpFold &f) { folds.push_back(f); });
+        }
+        if (jobs.size() > 0x7fffffffu || folds.size() > 0x7fffffffu) return WVG_ERR_SPACE;
+        // (the buffers below may still be in use by a call of the previous upload only
+        // through a caller's stream: the upload's quiesce waited for it)
+        const size_t jb = sizeof(TpJob) * jobs.size(), fb = sizeof(TpFold) * folds.size();
+        const size_t rb = sizeof(TpRecord) * (folds.size() ? folds.size() : 1);
+        if (!b->tp_stage.resize(jb + fb + 1) || !b->htpeak.resize(rb)) return WVG_ERR_SPACE;
+        HIPCHK(c, ensure(b->d_tpjobs, b->cap_tpjobs, jb ? jb : 1));
+        HIPCHK(c, ensure(b->d_tpfolds, b->cap_tpfolds, fb ? fb : 1));
+        HIPCHK(c, ensure(b->d_tppart, b->cap_tppart, sizeof(TpRecord) * (size_t)(part ? part : 1)));
+        HIPCHK(c, ensure(b->d_tpeak, b->cap_tpeak, rb));
+        // on the batch stream, behind the upload's copies; `up` is recorded again so that a
+        // call on a caller's stream waits for the tables too (as wvg_batch_levels' jobs)
+        if (jb) {
+            memcpy(b->tp_stage.data(), jobs.data(), jb);
+            HIPCHK(c, hipMemcpyAsync(b->d_tpjobs, b->tp_stage.data(), jb, hipMemcpyHostToDevice, b->stream));
+        }
+        if (fb) {
+            memcpy(b->tp_stage.data() + jb, folds.data(), fb);
+            HIPCHK(c, hipMemcpyAsync(b->d_tpfolds, b->tp_stage.data() + jb, fb, hipMemcpyHostToDevice, b->stream));
+        }
+        HIPCHK(c, hipEventRecord(b->up, b->stream));
+        b->tp_njobs = (uint32_t)jobs.size();
+        b->tp_nfolds = (uint32_t)folds.size();
+        b->tp_jobs_sent = true;
+    }
+    // after the whole of the last decode, and of whatever ran on the batch since (`done`):
+    // an earlier wvg_batch_true_peak has then downloaded its records, so this one may rewrite them
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_true_peak(b->d_tpjobs, b->tp_njobs, b->d_tpfolds, b->tp_nfolds, b->d_out, b->d_tppart, b->d_tpeak,
+                               (uint32_t)oversample, s));
+    if (b->tp_nfolds)
+        HIPCHK(c, hipMemcpyAsync(b->htpeak.data(), b->d_tpeak, sizeof(TpRecord) * (size_t)b->tp_nfolds,
+                                 hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
+    b->tp_issued = true;
+    return WVG_OK;
+}
+
+int wvg_batch_file_true_peak(wvg_batch *b, int file, wvg_channel_true_peak *out, int cap_channels) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || cap_channels < 0 || (cap_channels && !out) || !b->tp_issued)
+        return WVG_ERR_ARG;
+    const int64_t r0 = b->tp_rec0[(size_t)file];
+    if (r0 < 0) return WVG_ERR_OPEN;
+    const int nch = b->finfo[(size_t)file].out_nch, n = nch < cap_channels ? nch : cap_channels;
+    if (n > 0) memcpy(out, b->htpeak.data() + sizeof(TpRecord) * (size_t)r0, sizeof(TpRecord) * (size_t)n);
+    return nch;
+}
+
+int wvg_true_peak_taps(int32_t taps[48]) {
+    if (!taps) return WVG_ERR_ARG;
+    for (uint32_t q = 0; q < 4u; q++)
+        for (uint32_t t = 0; t < kTpTaps_n; t++) taps[q * kTpTaps_n + t] = kTpTaps[q][t];
+    return WVG_OK;
+}
+
+int wvg_true_peak_oversample(int64_t rate) { return (int)tp_oversample(rate); }
+
+int wvg_true_peak_tile_frames(int channels) {
+    if (channels < 1 || channels > (int)kTpMaxChannels) return WVG_ERR_ARG;
+    return (int)tp_tile_frames((uint32_t)channels);
+}
+
+int wvg_true_peak_ints(const int32_t *src, int64_t frames, int channels, int k, int oversample,
+                       wvg_channel_true_peak *out) {
+    if (channels < 1 || channels > (int)kTpMaxChannels || frames < 0 || (k != 7 && k != 15 && k != 23 && k != 31) ||
+        (oversample != 1 && oversample != 2 && oversample != 4) || (frames && !src) || !out)
+        return WVG_ERR_ARG;
+    if (!tp_tile_fits((uint32_t)channels)) return WVG_ERR_SPACE;
+    // the kernels' code (wv_tpeak.h), the workgroup's threads as loops
+    const uint32_t O = (uint32_t)oversample;
+    std::vector<TpJob> jobs;
+    std::vector<TpFold> folds;
+    const uint64_t nparts = tp_file_jobs(0, (uint64_t)frames, (uint32_t)channels, (uint32_t)k, O, 0,
+                                         [&](const TpJob &j) { jobs.push_back(j); },
+                                         [&](const TpFold &f) { folds.push_back(f); });
+    std::vector<TpRecord> partials((size_t)nparts);
+    std::vector<int32_t> tile(kTpLdsInts);
+    std::vector<TpAcc> acc(kTpThreads), nxt(kTpThreads);
+    for (const TpJob &j : jobs) {
+        bool wide = false;
+        for (uint32_t tid = 0; tid < kTpThreads; tid++) wide |= tp_load(j, src + j.in_off, tile.data(), tid, kTpThreads);
+        for (uint32_t tid = 0; tid < kTpThreads; tid++) acc[tid] = tp_scan(j, tile.data(), tid, O, wide);
+        const uint32_t lanes = tp_tree_lanes(j.nch), waves = tp_row_waves(j.nch), segs = tp_segments(j.nch);
+        for (uint32_t m = kTpWave / 2; m; m >>= 1) {
+            if (lanes <= m) continue;
+            for (uint32_t tid = 0; tid < kTpThreads; tid++) nxt[tid] = tp_merge(acc[tid], acc[tid ^ m]);
+            acc.swap(nxt);
+        }
+        for (uint32_t tid = 0; tid < kTpThreads; tid++) {
+            if (waves > 1u) {
+                if (tid >= j.nch) continue;
+                TpAcc a = acc[tid * waves * kTpWave];
+                for (uint32_t w = 1; w < waves; w++) a = tp_merge(a, acc[(tid * waves + w) * kTpWave]);
+                tp_partial(j, a, O, partials.data() + j.part + tid);
+            } else {
+                const uint32_t c = tid / segs;
+                if (c < j.nch && tid == c * segs) tp_partial(j, acc[tid], O, partials.data() + j.part + c);
+            }
+        }
+    }
+    std::vector<TpRecord> lane(kTpCombineLanes), lnxt(kTpCombineLanes);
+    for (size_t r = 0; r < folds.size(); r++) {
+        for (uint32_t l = 0; l < kTpCombineLanes; l++) lane[l] = tp_fold(folds[r], partials.data(), l, kTpCombineLanes);
+        for (uint32_t m = kTpCombineLanes / 2; m; m >>= 1) {
+            for (uint32_t l = 0; l < kTpCombineLanes; l++) lnxt[l] = tp_rec_merge(lane[l], lane[l ^ m]);
+            lane.swap(lnxt);
+        }
+        tp_final(folds[r], lane[0], O, reinterpret_cast<TpRecord *>(out) + r);
     }
     return WVG_OK;
 }
