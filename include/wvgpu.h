@@ -758,6 +758,62 @@ int wvg_loudness_ints(const int32_t *src, int64_t frames, int channels, int k, i
 int wvg_loudness_gate(const double *blocks, int64_t n, wvg_file_loudness *out);
 int wvg_loudness_run_steps(void);
 
+/* ---- Loudness range and short-term loudness on the device (beyond the reference): EBU Tech
+ * 3342's loudness range (LRA) and the short-term series it is made from, which with
+ * max_block_power (the maximum momentary loudness) complete EBU R 128's descriptors -- 64
+ * bytes per file, three more kernels per batch (wv_lra.hip) over the step energies that
+ * wvg_batch_loudness leaves on the device, and no PCM or series downloaded.
+ *   A file is measurable exactly by loudness's rule; S, nsteps, the weights G_c and the step
+ * energies E[c][j] are wvg_batch_loudness's, runs and their restarts included.
+ *   Short-term power: a window is 30 steps (3 s), the hop one step (100 ms).  nshort =
+ * max(0, nsteps - 29); for 0 <= j < nshort, ST_j = acc / (double)(30 * S) with acc = +0.0
+ * and, for c ascending, t = E[c][j], t = t + E[c][j+i] for i = 1 .. 29 ascending, acc =
+ * fma(G_c, t, acc).
+ *   Gates, in the linear domain, strict > as the integrated gate's: ABS as above.
+ * abs_shorts = #{ST_j > ABS}, ungated_short_power = their mean or 0.0 for none, summed as
+ * loudness's gate sums (64 partial sums, partial l adds ST_l, ST_(l+64), ... in that order,
+ * joined by the butterfly l with l ^ 32, ^ 16, ... ^ 1; mean = sum / (double)count).  rel =
+ * 0.01 * ungated_short_power (-20 LU).  The gated multiset G = {ST_j : ST_j > ABS and ST_j >
+ * rel}, gated_shorts = n = |G|; max_short_power = max ST_j, 0.0 for nshort = 0.
+ *   Percentiles, exact (libebur128's index rule in integers): with g_0 <= ... <= g_(n-1) the
+ * sorted G, low_power = g[(n + 4) / 10] and high_power = g[(19 * (n - 1) + 10) / 20], integer
+ * divisions, both 0.0 for n = 0.  An order statistic does not depend on how it is found: the
+ * device finds both by a radix select over the doubles' bit patterns (no ST_j is negative,
+ * so they order as unsigned integers).  LRA = 10 log10(high_power / low_power) LU, the
+ * short-term loudness -0.691 + 10 log10(ST_j) LUFS: the caller's (api.scan_loudness).
+ *   wvg_batch_loudness_range is ordered exactly as wvg_batch_loudness, and returns without
+ * waiting (wvg_batch_sync covers it; the next reset / upload waits for it).  It reads the
+ * step energies of a wvg_batch_loudness issued on this batch after the batch's latest
+ * wvg_batch_decode; where there is none it issues exactly that call first, on the same
+ * stream, and that call's records become readable too.  Every record and every ST_j is
+ * written by every call; the short-term image (every measurable file's ST_j, file after
+ * file) stays on the device and is overwritten by the next call.  WVG_ERR_ARG before an
+ * upload.
+ *   wvg_batch_file_loudness_range, after wvg_batch_sync: WVG_ERR_OPEN for a file that is not
+ * measurable, WVG_ERR_ARG when no wvg_batch_loudness_range ran since the last upload.
+ * wvg_batch_loudness_shorts: the doubles of the short-term image;
+ * wvg_batch_download_loudness_shorts waits for the batch's work and copies them
+ * (WVG_ERR_SPACE: cap too small).
+ *   Host only: wvg_loudness_range_ints runs the kernels' code (wv_loud.h, wv_lra.h) on the
+ * host over `frames` x `channels` interleaved ints and fills the record (short_offset 0) and
+ * the nshort short-term powers (WVG_ERR_SPACE: cap_shorts < nshort); wvg_loudness_range_gate
+ * runs the gates and the selection over any list of short-term powers -- an album's, or
+ * values with no audio behind them -- and fills the four powers and the three counts
+ * (short_offset 0; WVG_ERR_SPACE for n >= 2^32). */
+typedef struct {              /* 64 bytes, one per measurable file */
+    double  low_power, high_power, max_short_power, ungated_short_power;
+    int64_t shorts, abs_shorts, gated_shorts;
+    int64_t short_offset;     /* the file's first ST_j in the short-term image */
+} wvg_file_loudness_range;
+
+int wvg_batch_loudness_range(wvg_batch *b, void *stream);
+int wvg_batch_file_loudness_range(wvg_batch *b, int file, wvg_file_loudness_range *out);
+int64_t wvg_batch_loudness_shorts(const wvg_batch *b);
+int wvg_batch_download_loudness_shorts(wvg_batch *b, double *host, int64_t cap);
+int wvg_loudness_range_ints(const int32_t *src, int64_t frames, int channels, int k, int64_t rate,
+                            uint32_t channel_mask, wvg_file_loudness_range *out, double *shorts, int64_t cap_shorts);
+int wvg_loudness_range_gate(const double *shorts, int64_t n, wvg_file_loudness_range *out);
+
 /* WvDemo.Main (WvDemo.cs:15-168) for one file of a formatted batch built with
  * chunk_frames 4096: the .wav bytes it writes (stored RIFF header or the
  * synthesized RIFF/fmt/data headers, the PCM, the stored trailer) and its exit

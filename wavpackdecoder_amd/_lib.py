@@ -71,6 +71,11 @@ LOUDNESS_DTYPE = [("power", "<f8"), ("ungated_power", "<f8"), ("max_block_power"
                   ("abs_blocks", "<i8"), ("gated_blocks", "<i8"), ("block_offset", "<i8"), ("step_frames", "<i4"),
                   ("channels", "<i4")]
 
+# wvg_file_loudness_range (include/wvgpu.h): one 64-byte record per measurable file
+LOUDNESS_RANGE_DTYPE = [("low_power", "<f8"), ("high_power", "<f8"), ("max_short_power", "<f8"),
+                        ("ungated_short_power", "<f8"), ("shorts", "<i8"), ("abs_shorts", "<i8"),
+                        ("gated_shorts", "<i8"), ("short_offset", "<i8")]
+
 
 class WvgFileResult(ctypes.Structure):
     _fields_ = [
@@ -204,6 +209,12 @@ def lib():
         "wvg_loudness_ints": (i32, [vp, i64, i32, i32, i64, u32, vp, vp, i64]),
         "wvg_loudness_gate": (i32, [vp, i64, vp]),
         "wvg_loudness_run_steps": (i32, []),
+        "wvg_batch_loudness_range": (i32, [vp, vp]),
+        "wvg_batch_file_loudness_range": (i32, [vp, i32, vp]),
+        "wvg_batch_loudness_shorts": (i64, [vp]),
+        "wvg_batch_download_loudness_shorts": (i32, [vp, vp, i64]),
+        "wvg_loudness_range_ints": (i32, [vp, i64, i32, i32, i64, u32, vp, vp, i64]),
+        "wvg_loudness_range_gate": (i32, [vp, i64, vp]),
         "wvg_dsd_pcm_taps": (i32, [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)]),
         "wvg_dsd_pcm_ints": (i32, [vp, i64, i32, vp]),
         "wvg_dsd_pcm_tile_frames": (i32, [i32]),
@@ -243,6 +254,8 @@ EXPORTED = ("wvg_open", "wvg_close", "wvg_last_error", "wvg_batch_new", "wvg_bat
             "wvg_batch_loudness", "wvg_batch_file_loudness", "wvg_batch_loudness_blocks",
             "wvg_batch_download_loudness_blocks", "wvg_loudness_filter", "wvg_loudness_weights", "wvg_loudness_ints",
             "wvg_loudness_gate", "wvg_loudness_run_steps",
+            "wvg_batch_loudness_range", "wvg_batch_file_loudness_range", "wvg_batch_loudness_shorts",
+            "wvg_batch_download_loudness_shorts", "wvg_loudness_range_ints", "wvg_loudness_range_gate",
             "wvg_dsd_pcm_taps", "wvg_dsd_pcm_ints", "wvg_dsd_pcm_tile_frames",
             "wvg_stream_open", "wvg_stream_unpack", "wvg_stream_set_sample", "wvg_stream_state", "wvg_stream_close")
 # The MD5 entry points, listed apart: tests/test_abi.py's header scan matches names of

@@ -620,6 +620,48 @@ class DecodeBatch:
         o, n = int(rec["block_offset"]), int(rec["blocks"])
         return self.download_loudness_blocks()[o: o + n].copy()
 
+    def loudness_range(self, stream=None):
+        """Every measurable file's loudness range and short-term series (EBU Tech 3342) on the
+        device (wvg_batch_loudness_range; the definition: include/wvgpu.h), after decode(), on
+        `stream`, without waiting -- sync() covers it.  Where no loudness() was issued since
+        the last decode() it is issued first, and file_loudness() is readable too."""
+        if not self._uploaded:
+            self.upload()
+        self._check(self._L.wvg_batch_loudness_range(self._b, stream))
+
+    def file_loudness_range(self, i: int):
+        """File i's record of the last loudness_range() (wvg_batch_file_loudness_range; after
+        sync()): one element of a structured array (_lib.LOUDNESS_RANGE_DTYPE), or None for a
+        file that is not measurable (loudness's rule)."""
+        out = np.zeros(1, dtype=_L.LOUDNESS_RANGE_DTYPE)
+        rc = self._L.wvg_batch_file_loudness_range(self._b, int(i), out.ctypes.data)
+        if rc == _L.WVG_ERR_OPEN:
+            return None
+        self._check(rc)
+        return out[0]
+
+    def download_loudness_shorts(self) -> np.ndarray:
+        """The short-term image of the last loudness_range(): every measurable file's short-term
+        powers ST_j, file after file, as float64 (wvg_batch_download_loudness_shorts; waits
+        for it)."""
+        n = self._L.wvg_batch_loudness_shorts(self._b)
+        if n < 0:
+            self._check(n)
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        self._check(self._L.wvg_batch_download_loudness_shorts(self._b, out.ctypes.data, out.size))
+        return out[:n]
+
+    def loudness_shorts(self, i: int):
+        """File i's short-term powers of the last loudness_range() (float64, one per 3 s window
+        every 100 ms), or None for a file that is not measurable.  Downloads the whole image:
+        a caller that wants many files' takes download_loudness_shorts() once and slices it
+        by the records' short_offset and shorts."""
+        rec = self.file_loudness_range(i)
+        if rec is None:
+            return None
+        o, n = int(rec["short_offset"]), int(rec["shorts"])
+        return self.download_loudness_shorts()[o: o + n].copy()
+
     def wav(self, i: int):
         """WvDemo.Main for file i (WvDemo.cs:15-168): (exit_code, .wav bytes)."""
         n, rc = ctypes.c_int64(), ctypes.c_int32()
@@ -1252,6 +1294,56 @@ def loudness_gate(blocks):
     return rec[0]
 
 
+def loudness_range_ints(src: np.ndarray, k: int, rate: int, channel_mask: int = 0):
+    """The loudness-range kernels' code run on the host (wvg_loudness_range_ints): `src` as
+    loudness_ints takes it.  Returns (record, short-term powers): one element of
+    _lib.LOUDNESS_RANGE_DTYPE and a float64 array."""
+    a = np.asarray(src)
+    if a.dtype != np.int32:
+        a = a.astype(np.int32)
+    a = a.reshape(-1, 1) if a.ndim == 1 else a
+    if not a.flags.c_contiguous:
+        a = np.ascontiguousarray(a)
+    frames, nch = a.shape
+    _, s = loudness_filter(rate)
+    n = max(frames // s - 29, 0)
+    rec, shorts = np.zeros(1, dtype=_L.LOUDNESS_RANGE_DTYPE), np.zeros(max(n, 1), dtype=np.float64)
+    rc = _L.lib().wvg_loudness_range_ints(a.ctypes.data, frames, nch, int(k), int(rate),
+                                          int(channel_mask) & 0xFFFFFFFF, rec.ctypes.data, shorts.ctypes.data, n)
+    if rc != 0:
+        raise ValueError(f"wvg_loudness_range_ints: {rc}")
+    return rec[0], shorts[:n]
+
+
+def loudness_range_gate(shorts):
+    """The gates and the percentile selection over any list of short-term powers
+    (wvg_loudness_range_gate), an album's for one: one element of _lib.LOUDNESS_RANGE_DTYPE
+    with the four powers and the three counts filled."""
+    p = np.ascontiguousarray(np.asarray(shorts, dtype=np.float64).reshape(-1))
+    rec = np.zeros(1, dtype=_L.LOUDNESS_RANGE_DTYPE)
+    rc = _L.lib().wvg_loudness_range_gate(p.ctypes.data if p.size else None, p.size, rec.ctypes.data)
+    if rc != 0:
+        raise ValueError(f"wvg_loudness_range_gate: {rc}")
+    return rec[0]
+
+
+def _power_lufs(p: float) -> float:
+    return -0.691 + 10.0 * math.log10(p) if p > 0 else float("-inf")
+
+
+def _range_fields(d: dict, rec) -> None:
+    """the loudness-range record's fields and what R 128 calls them, into a scan_loudness dict"""
+    for n in rec.dtype.names:
+        d[n] = float(rec[n]) if rec.dtype[n].kind == "f" else int(rec[n])
+    d["range_record"] = rec
+    ok = d["gated_shorts"] > 0 and d["low_power"] > 0
+    d["lra_lu"] = 10.0 * math.log10(d["high_power"] / d["low_power"]) if ok else 0.0
+    d["lra_low_lufs"] = _power_lufs(d["low_power"])
+    d["lra_high_lufs"] = _power_lufs(d["high_power"])
+    d["max_short_term_lufs"] = _power_lufs(d["max_short_power"])
+    d["max_momentary_lufs"] = _power_lufs(d["max_block_power"])
+
+
 def _lufs_dict(rec, target_lufs: float) -> dict:
     d = {n: (float(rec[n]) if rec.dtype[n].kind == "f" else int(rec[n])) for n in rec.dtype.names}
     lufs = -0.691 + 10.0 * math.log10(d["power"]) if d["gated_blocks"] > 0 and d["power"] > 0 else float("-inf")
@@ -1267,7 +1359,7 @@ def _clip_safe(d: dict, tp_dbtp: float) -> None:
 
 
 def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album: bool = False,
-                  true_peak: bool = False) -> list:
+                  true_peak: bool = False, loudness_range: bool = False) -> list:
     """Decode `files` and measure each one's integrated loudness on the device: add, upload,
     decode, loudness and sync, with no PCM formatted or downloaded.  Returns one dict per
     file, None for a file that is not measurable: the record's fields by name (and `record`
@@ -1278,14 +1370,22 @@ def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album:
     With true_peak=True the true peak (DecodeBatch.true_peak, each file's own oversampling
     factor) is queued on the same decode, and each dict gains `true_peak_dbtp`, the maximum
     over the file's channels, and `clip_safe_gain_db` = min(gain_db, -true_peak_dbtp) (None
-    where gain_db is None); the album dict gains the maximum over the files."""
+    where gain_db is None); the album dict gains the maximum over the files.
+    With loudness_range=True the loudness range (DecodeBatch.loudness_range, EBU Tech 3342) is
+    queued on the same decode, and each dict gains that record's fields (and `range_record`),
+    `lra_lu` = 10 log10(high_power / low_power) (0.0 when no short-term value passed the
+    gates), `lra_low_lufs`, `lra_high_lufs`, `max_short_term_lufs` and `max_momentary_lufs`
+    (from max_block_power), each -0.691 + 10 log10(power) or -inf; the album dict takes
+    loudness_range_gate over the short-term powers of all measurable files together."""
     b = DecodeBatch(SAMPLE_BUFFER_SIZE)
     try:
-        res, recs, peaks = [], [], []
+        res, recs, peaks, ranges = [], [], [], []
         if len(files):
             idx = b.add_files(files, open_flags)
             b.decode()
             b.loudness()
+            if loudness_range:
+                b.loudness_range()
             if true_peak:
                 b.true_peak(0)
             b.sync()
@@ -1296,6 +1396,9 @@ def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album:
                 if true_peak and rec is not None:
                     peaks.append(_true_peak_dict(b.file_true_peak(i), b.infos[i])["max_dbtp"])
                     _clip_safe(res[-1], peaks[-1])
+                if loudness_range and rec is not None:
+                    ranges.append(b.file_loudness_range(i))
+                    _range_fields(res[-1], ranges[-1])
         if album:
             img = b.download_loudness_blocks() if any(r is not None for r in recs) else np.zeros(0)
             parts = [img[int(r["block_offset"]): int(r["block_offset"]) + int(r["blocks"])] for r in recs
@@ -1303,6 +1406,10 @@ def scan_loudness(files, open_flags: int = 0, target_lufs: float = -18.0, album:
             res.append(_lufs_dict(loudness_gate(np.concatenate(parts) if parts else np.zeros(0)), target_lufs))
             if true_peak:
                 _clip_safe(res[-1], max(peaks) if peaks else float("-inf"))
+            if loudness_range:
+                img = b.download_loudness_shorts() if ranges else np.zeros(0)
+                parts = [img[int(r["short_offset"]): int(r["short_offset"]) + int(r["shorts"])] for r in ranges]
+                _range_fields(res[-1], loudness_range_gate(np.concatenate(parts) if parts else np.zeros(0)))
         return res
     finally:
         b.close()

@@ -24,6 +24,7 @@
 #include "wv_levels.h"
 #include "wv_tpeak.h"
 #include "wv_loud.h"
+#include "wv_lra.h"
 #include "wv_mc.h"
 #include "wv_md5.h"
 #include "wv_planar.h"
@@ -55,6 +56,9 @@ hipError_t launch_true_peak(const TpJob *jobs, uint32_t njobs, const TpFold *fol
 hipError_t launch_loudness(const LdFile *files, uint32_t nfiles, const LdRun *runs, uint32_t nruns, uint64_t nblocks,
                            const double *coefs, const double *weights, const int32_t *in, double *E, double *P,
                            LdRecord *out, hipStream_t s);
+hipError_t launch_loudness_range(const LdFile *files, const LrFile *lr, uint32_t nfiles, uint64_t nshorts,
+                                 const double *weights, const double *E, double *ST, double *rel, LrRecord *out,
+                                 hipStream_t s);
 hipError_t launch_copy_to_host(const uint8_t *src, uint8_t *dst, size_t n, hipStream_t s);
 hipError_t launch_zero_fill(const ZeroSeg *segs, uint32_t nseg, int32_t *out, hipStream_t s);
 hipError_t upload_dsd_ptables();
@@ -379,6 +383,19 @@ struct wvg_batch {
     uint32_t ld_nfiles = 0, ld_nruns = 0;
     uint64_t ld_nblocks = 0;
     bool ld_jobs_sent = false, ld_issued = false;
+    // wvg_batch_loudness_range (wv_lra.h): one LrFile per measurable file behind loudness's
+    // table, built and sent with it; the short-term image, the relative gates and the records
+    // are shared by the calls as loudness's are.  decode_serial counts the batch's decodes and
+    // ld_serial is its value at the latest wvg_batch_loudness: the range call reads that
+    // call's step energies only when no decode was issued since.
+    double *d_lrST = nullptr, *d_lrrel = nullptr;
+    LrRecord *d_lra = nullptr;
+    size_t cap_lrST = 0, cap_lrrel = 0, cap_lra = 0;
+    size_t ld_lr_at = 0;  // byte offset of the LrFile table in d_ldtab
+    PinnedBuf hlra;
+    uint64_t lr_nshorts = 0;
+    uint64_t decode_serial = 0, ld_serial = 0;
+    bool lr_issued = false;
 };
 
 static int hip_fail(wvg_ctx *c, hipError_t e, const char *what) {
@@ -591,6 +608,16 @@ static void ld_design(int64_t rate, double *cf) {
 
 static uint32_t ld_step_frames(int64_t rate) { return (uint32_t)((rate + 5) / 10); }
 
+// one file's entry in the short-term table (wv_lra.h); `st_off`: where its ST_j start, it advances
+static LrFile lr_file_entry(uint32_t nsteps, uint64_t &st_off) {
+    LrFile f;
+    f.st_off = st_off;
+    f.nshort = lr_nshort(nsteps);
+    f.pad = 0;
+    st_off += f.nshort;
+    return f;
+}
+
 extern "C" {
 
 wvg_ctx *wvg_open(int device) {
@@ -786,6 +813,13 @@ static void free_dev(wvg_batch *b) {
     b->d_loud = nullptr;
     b->cap_ldtab = b->cap_ldE = b->cap_ldP = b->cap_loud = 0;
     b->ld_jobs_sent = b->ld_issued = false;
+    hipFree(b->d_lrST);
+    hipFree(b->d_lrrel);
+    hipFree(b->d_lra);
+    b->d_lrST = b->d_lrrel = nullptr;
+    b->d_lra = nullptr;
+    b->cap_lrST = b->cap_lrrel = b->cap_lra = 0;
+    b->lr_issued = false;
     hipFree(b->d_md5jobs);
     hipFree(b->d_md5);
     b->d_md5jobs = nullptr;
@@ -1039,7 +1073,7 @@ int wvg_batch_reset(wvg_batch *b) {
     b->md5_jobs_sent = b->md5_issued = false;
     b->lv_jobs_sent = b->lv_issued = false;
     b->tp_jobs_sent = b->tp_issued = false;
-    b->ld_jobs_sent = b->ld_issued = false;
+    b->ld_jobs_sent = b->ld_issued = b->lr_issued = false;
     planar_forget(b);
     return WVG_OK;
 }
@@ -1573,7 +1607,7 @@ int wvg_batch_upload(wvg_batch *b) {
     b->md5_jobs_sent = b->md5_issued = false;
     b->lv_jobs_sent = b->lv_issued = false;
     b->tp_jobs_sent = b->tp_issued = false;
-    b->ld_jobs_sent = b->ld_issued = false;
+    b->ld_jobs_sent = b->ld_issued = b->lr_issued = false;
     planar_forget(b);
     // the blob is followed by 64 B of 0xFF (the reader's past-end fill)
     HIPCHK(c, blob_push(b));  // what the adds have not sent yet
@@ -1806,6 +1840,7 @@ int wvg_batch_decode(wvg_batch *b, void *stream) {
     HIPCHK(c, hipSetDevice(c->device));  // side streams and events belong to the batch's device, whatever the calling thread
     hipStream_t s = stream ? (hipStream_t)stream : b->stream;
     if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));  // the upload's copies (not waited for)
+    b->decode_serial++;  // step energies of an earlier wvg_batch_loudness are stale from here on
     if (b->timing) {
         // a bounded number of pairs stays pending: the oldest is folded into the
         // running sum (it finished long ago) and its events are reused
@@ -3262,8 +3297,9 @@ int wvg_batch_loudness(wvg_batch *b, void *stream) {
         std::vector<LdRun> runs;
         std::vector<int64_t> rates;
         std::vector<double> coefs, weights;
+        std::vector<LrFile> shorts;
         b->ld_rec.assign(nf, -1);
-        uint64_t e_off = 0, blk_off = 0, w_off = 0;
+        uint64_t e_off = 0, blk_off = 0, w_off = 0, st_off = 0;
         for (size_t i = 0; i < nf; i++) {
             if (!ld_measurable(b, i)) continue;
             const FileInfo &fi = b->finfo[i];
@@ -3283,18 +3319,24 @@ int wvg_batch_loudness(wvg_batch *b, void *stream) {
             files.push_back(ld_file_jobs((uint32_t)files.size(), (uint64_t)b->infos[i].out_offset,
                                          (uint64_t)fi.out_frames, (uint32_t)fi.out_nch, pl_kind(b, i), S, (uint32_t)ci,
                                          e_off, blk_off, w_off, [&](const LdRun &r) { runs.push_back(r); }));
+            shorts.push_back(lr_file_entry(files.back().nsteps, st_off));
         }
         if (runs.size() > 0x7fffffffu) return WVG_ERR_SPACE;
         // (the buffers below may still be in use by a call of the previous upload only
         // through a caller's stream: the upload's quiesce waited for it)
         const size_t fb = sizeof(LdFile) * files.size(), rb = sizeof(LdRun) * runs.size();
         const size_t cb = sizeof(double) * coefs.size(), wb = sizeof(double) * weights.size();
-        const size_t tb = fb + rb + cb + wb, ob = sizeof(LdRecord) * (files.size() ? files.size() : 1);
-        if (!b->ld_stage.resize(tb + 1) || !b->hloud.resize(ob)) return WVG_ERR_SPACE;
+        const size_t lb = sizeof(LrFile) * shorts.size(), nrec = files.size() ? files.size() : 1;
+        const size_t tb = fb + rb + cb + wb + lb, ob = sizeof(LdRecord) * nrec;
+        if (!b->ld_stage.resize(tb + 1) || !b->hloud.resize(ob) || !b->hlra.resize(sizeof(LrRecord) * nrec))
+            return WVG_ERR_SPACE;
         HIPCHK(c, ensure(b->d_ldtab, b->cap_ldtab, tb ? tb : 1));
         HIPCHK(c, ensure(b->d_ldE, b->cap_ldE, sizeof(double) * (size_t)(e_off ? e_off : 1)));
         HIPCHK(c, ensure(b->d_ldP, b->cap_ldP, sizeof(double) * (size_t)(blk_off ? blk_off : 1)));
         HIPCHK(c, ensure(b->d_loud, b->cap_loud, ob));
+        HIPCHK(c, ensure(b->d_lrST, b->cap_lrST, sizeof(double) * (size_t)(st_off ? st_off : 1)));
+        HIPCHK(c, ensure(b->d_lrrel, b->cap_lrrel, sizeof(double) * nrec));
+        HIPCHK(c, ensure(b->d_lra, b->cap_lra, sizeof(LrRecord) * nrec));
         // on the batch stream, behind the upload's copies; `up` is recorded again so that a
         // call on a caller's stream waits for the table too (as wvg_batch_levels' jobs)
         if (tb) {
@@ -3303,12 +3345,15 @@ int wvg_batch_loudness(wvg_batch *b, void *stream) {
             if (rb) memcpy(st + fb, runs.data(), rb);
             if (cb) memcpy(st + fb + rb, coefs.data(), cb);
             if (wb) memcpy(st + fb + rb + cb, weights.data(), wb);
+            if (lb) memcpy(st + fb + rb + cb + wb, shorts.data(), lb);
             HIPCHK(c, hipMemcpyAsync(b->d_ldtab, st, tb, hipMemcpyHostToDevice, b->stream));
         }
         HIPCHK(c, hipEventRecord(b->up, b->stream));
         b->ld_runs_at = fb;
         b->ld_coef_at = fb + rb;
         b->ld_w_at = fb + rb + cb;
+        b->ld_lr_at = fb + rb + cb + wb;
+        b->lr_nshorts = st_off;
         b->ld_nfiles = (uint32_t)files.size();
         b->ld_nruns = (uint32_t)runs.size();
         b->ld_nblocks = blk_off;
@@ -3328,6 +3373,7 @@ int wvg_batch_loudness(wvg_batch *b, void *stream) {
                                  hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipEventRecord(b->done, s));  // wvg_batch_sync and the next quiesce wait for it
     b->ld_issued = true;
+    b->ld_serial = b->decode_serial;
     return WVG_OK;
 }
 
@@ -3419,6 +3465,155 @@ int wvg_loudness_ints(const int32_t *src, int64_t frames, int channels, int k, i
         blocks[idx] = ld_block(g, E.data() + g.e_off, w.data() + g.w_off, (uint32_t)(idx - g.blk_off));
     }
     ld_gate_host(&f, blocks, blk_n, reinterpret_cast<LdRecord *>(out));
+    return WVG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Loudness range and short-term loudness of the decoded batch on the device (wv_lra.hip)
+// ---------------------------------------------------------------------------
+static_assert(sizeof(wvg_file_loudness_range) == 64 && sizeof(LrRecord) == 64, "one record is 64 bytes");
+static_assert(offsetof(wvg_file_loudness_range, high_power) == offsetof(LrRecord, high_power) &&
+                  offsetof(wvg_file_loudness_range, max_short_power) == offsetof(LrRecord, max_short_power) &&
+                  offsetof(wvg_file_loudness_range, ungated_short_power) == offsetof(LrRecord, ungated_short_power) &&
+                  offsetof(wvg_file_loudness_range, shorts) == offsetof(LrRecord, shorts) &&
+                  offsetof(wvg_file_loudness_range, abs_shorts) == offsetof(LrRecord, abs_shorts) &&
+                  offsetof(wvg_file_loudness_range, gated_shorts) == offsetof(LrRecord, gated_shorts) &&
+                  offsetof(wvg_file_loudness_range, short_offset) == offsetof(LrRecord, short_offset),
+              "LrRecord is wvg_file_loudness_range");
+static_assert(sizeof(LrFile) == 16, "the short-term table is packed behind the weights");
+
+int wvg_batch_loudness_range(wvg_batch *b, void *stream) {
+    if (!b || !b->uploaded) return WVG_ERR_ARG;
+    wvg_ctx *c = b->ctx;
+    // the step energies of a wvg_batch_loudness issued after the latest decode, or that call first
+    if (!b->ld_issued || b->ld_serial != b->decode_serial) {
+        const int rc = wvg_batch_loudness(b, stream);
+        if (rc != WVG_OK) return rc;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : b->stream;
+    // behind that loudness call and whatever ran on the batch since (`done`): an earlier range
+    // call has then downloaded its records, so this one may rewrite them
+    if (s != b->stream) HIPCHK(c, hipStreamWaitEvent(s, b->up, 0));
+    HIPCHK(c, hipStreamWaitEvent(s, b->done, 0));
+    HIPCHK(c, launch_loudness_range(reinterpret_cast<const LdFile *>(b->d_ldtab),
+                                    reinterpret_cast<const LrFile *>(b->d_ldtab + b->ld_lr_at), b->ld_nfiles,
+                                    b->lr_nshorts, reinterpret_cast<const double *>(b->d_ldtab + b->ld_w_at), b->d_ldE,
+                                    b->d_lrST, b->d_lrrel, b->d_lra, s));
+    if (b->ld_nfiles)
+        HIPCHK(c, hipMemcpyAsync(b->hlra.data(), b->d_lra, sizeof(LrRecord) * (size_t)b->ld_nfiles,
+                                 hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(b->done, s));
+    b->lr_issued = true;
+    return WVG_OK;
+}
+
+int wvg_batch_file_loudness_range(wvg_batch *b, int file, wvg_file_loudness_range *out) {
+    if (!b || file < 0 || file >= (int)b->finfo.size() || !out || !b->lr_issued) return WVG_ERR_ARG;
+    const int64_t r = b->ld_rec[(size_t)file];
+    if (r < 0) return WVG_ERR_OPEN;
+    memcpy(out, b->hlra.data() + sizeof(LrRecord) * (size_t)r, sizeof(LrRecord));
+    return WVG_OK;
+}
+
+int64_t wvg_batch_loudness_shorts(const wvg_batch *b) {
+    if (!b || !b->lr_issued) return WVG_ERR_ARG;
+    return (int64_t)b->lr_nshorts;
+}
+
+int wvg_batch_download_loudness_shorts(wvg_batch *b, double *host, int64_t cap) {
+    if (!b || !b->lr_issued || (!host && b->lr_nshorts)) return WVG_ERR_ARG;
+    if (cap < (int64_t)b->lr_nshorts) return WVG_ERR_SPACE;
+    wvg_ctx *c = b->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamWaitEvent(b->stream, b->done, 0));
+    if (b->lr_nshorts)
+        HIPCHK(c, hipMemcpyAsync(host, b->d_lrST, sizeof(double) * (size_t)b->lr_nshorts, hipMemcpyDeviceToHost,
+                                 b->stream));
+    HIPCHK(c, hipStreamSynchronize(b->stream));
+    return WVG_OK;
+}
+
+// the gate and the select kernels' code over `n` short-term powers, their threads as loops
+static void lr_gate_host(const LrFile *f, const double *ST, uint64_t n, LrRecord *out) {
+    LdGate lane[kLdGateLanes], nxt[kLdGateLanes];
+    LdGate tot[2];
+    double rel = 0.0;
+    for (int pass = 0; pass < 2; pass++) {
+        for (uint32_t l = 0; l < kLdGateLanes; l++) lane[l] = ld_gate_part(ST, n, l, kLdGateLanes, rel);
+        for (uint32_t m = kLdGateLanes / 2; m; m >>= 1) {
+            for (uint32_t l = 0; l < kLdGateLanes; l++) nxt[l] = ld_gate_merge(lane[l], lane[l ^ m]);
+            memcpy(lane, nxt, sizeof lane);
+        }
+        tot[pass] = lane[0];
+        rel = lr_rel(tot[0]);
+    }
+    lr_record(f, n, tot[0], tot[1], out);
+    const uint64_t g = (uint64_t)tot[1].cnt;
+    if (!g) return;
+    LrRank lo, hi;
+    lo.prefix = hi.prefix = 0;
+    lo.rank = lr_low_rank(g);
+    hi.rank = lr_high_rank(g);
+    std::vector<uint32_t> hist(2 * kLrBins);
+    for (uint32_t pass = 0; pass < kLrPasses; pass++) {
+        std::fill(hist.begin(), hist.end(), 0u);
+        const bool same = lo.prefix == hi.prefix;
+        for (uint64_t j = 0; j < n; j++) {
+            if (!lr_gated(ST[j], rel)) continue;
+            const uint64_t u = lr_bits(ST[j]);
+            const uint32_t d = lr_digit(u, pass);
+            if (lr_candidate(u, lo, pass)) hist[d]++;
+            if (!same && lr_candidate(u, hi, pass)) hist[kLrBins + d]++;
+        }
+        // the walk, the wave's lanes as a loop and its scan as a running sum
+        LrRank *const rk[2] = {&lo, &hi};
+        for (int w = 0; w < 2; w++) {
+            const uint32_t *h = hist.data() + (w && !same ? kLrBins : 0u);
+            uint64_t before = 0;
+            for (uint32_t lane = 0; lane < kLrWalkLanes; lane++) {
+                if (lr_walk_lane(h, lane, before, *rk[w], pass)) break;
+                before += lr_walk_sum(h, lane);
+            }
+        }
+    }
+    out->low_power = lr_value(lo.prefix);
+    out->high_power = lr_value(hi.prefix);
+}
+
+int wvg_loudness_range_gate(const double *shorts, int64_t n, wvg_file_loudness_range *out) {
+    if (n < 0 || (n && !shorts) || !out) return WVG_ERR_ARG;
+    if ((uint64_t)n > 0xffffffffu) return WVG_ERR_SPACE;  // the bins count in 32 bits
+    lr_gate_host(nullptr, shorts, (uint64_t)n, reinterpret_cast<LrRecord *>(out));
+    return WVG_OK;
+}
+
+int wvg_loudness_range_ints(const int32_t *src, int64_t frames, int channels, int k, int64_t rate,
+                            uint32_t channel_mask, wvg_file_loudness_range *out, double *shorts, int64_t cap_shorts) {
+    if (channels < 1 || channels > (int)kLdMaxChannels || frames < 0 || (k != 7 && k != 15 && k != 23 && k != 31) ||
+        rate < kLdMinRate || rate > kLdMaxRate || (frames && !src) || !out || cap_shorts < 0 || (cap_shorts && !shorts))
+        return WVG_ERR_ARG;
+    const uint32_t S = ld_step_frames(rate);
+    if ((uint64_t)frames / S >= 0x7fffffffu) return WVG_ERR_SPACE;
+    double cf[kLdCoefDoubles] = {0};
+    ld_design(rate, cf);
+    std::vector<double> w((size_t)channels);
+    ld_weights((uint32_t)channels, channel_mask, w.data());
+    // the kernels' code (wv_loud.h, wv_lra.h), their threads as loops
+    std::vector<LdRun> runs;
+    uint64_t e_n = 0, blk_n = 0, w_n = 0, st_n = 0;
+    const LdFile f = ld_file_jobs(0, 0, (uint64_t)frames, (uint32_t)channels, (uint32_t)k, S, 0, e_n, blk_n, w_n,
+                                  [&](const LdRun &r) { runs.push_back(r); });
+    const LrFile lr = lr_file_entry(f.nsteps, st_n);
+    if ((int64_t)st_n > cap_shorts) return WVG_ERR_SPACE;
+    std::vector<double> E((size_t)e_n);
+    for (const LdRun &r : runs) ld_run(f, r, cf, src, E.data());
+    for (uint64_t idx = 0; idx < st_n; idx++) {
+        const uint32_t fi = lr_find_file(&lr, 1, idx);
+        const LdFile &g = (&f)[fi];
+        shorts[idx] = lr_short(g, E.data() + g.e_off, w.data() + g.w_off, (uint32_t)(idx - (&lr)[fi].st_off));
+    }
+    lr_gate_host(&lr, shorts, st_n, reinterpret_cast<LrRecord *>(out));
     return WVG_OK;
 }
 
